@@ -3,6 +3,7 @@
 forward + loss + backward + gradient all-reduce + AdamW) on N MI355X of one node.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full --dump-outputs DIR
     python bench.py --gpus N --steps K --warmup W          # starts its own N ranks (child processes, before any GPU call)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W             # or under a launcher (RANK / LOCAL_RANK / WORLD_SIZE from the environment)
@@ -12,14 +13,21 @@ operands with fp32 accumulation / residual stream / master weights, synthetic da
 (SURVEY.md 8d), weak scaling (per-GPU batch fixed).  A step is one engine iteration (reference
 engine_grid_masking.py:40-143): clean image on even steps, grid-masked image on odd steps.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): the driver's contract (metric, value, unit,
+higher_is_better, dtype, ms_per_step), the run's configuration and the FLOP rates derived from the measured step time.
+  --dump-outputs DIR  after the timed steps, write what the timed path returned -- the loop's meters, averaged over the timed
+                      steps -- as DIR/<meter>.npy (dump_outputs below); the inputs are seeded, so two runs or two builds can be
+                      compared output for output
+  --full              everything else the benchmark measures, each in runs of its own behind the timed region, adds to the line:
+  flops.blocks_only   two more iterations with HIP events around the Block kernels (see `flops` below)
   roofline      the largest single launch of the step (fused-MLP weight gradients of a stage-1 block) timed live with HIP events on
                 its launch stream: algorithmic vs executed FLOPs, PMC traffic; round 2's MFMA- and HBM-bound launches as `siblings`
   step          executed TFLOP/s and HBM GB per step (committed whole-step counter passes) over ms per step
   cpu_baseline  the CPU oracle (oracle/pvlt_oracle.py, kind "port") timed on this box's host cores at config #1
                 shapes (4 pairs), N=1 only: full train step (fwd+loss+bwd+AdamW) = `value`, forward+loss beside it
-  flops         reference-equivalent and EXECUTED FLOPs per pair, and the blocks-only (SRAttention + MLP) MFMA utilisation
-                north_star asks for: 3 x 8.003 GFLOP/pair over the GPU time between HIP events around the Block kernels
+  other_configs BASELINE configurations #4 / #5 and the eval forward, short runs at one GPU
+  flops         reference-equivalent and EXECUTED FLOPs per pair (plain run too), and with --full the blocks-only (SRAttention + MLP)
+                MFMA utilisation north_star asks for: 3 x 8.003 GFLOP/pair over the GPU time between HIP events around the Block kernels
 
 The timed region is `engine_grid_masking.train_one_epoch_vl` itself (the reference's entry point, main_vl.py:431-437) over
 a loader of K batches that are already resident in HBM: masked-index selection, loss read-back, zero_grad, backward,
@@ -369,6 +377,19 @@ def other_configs(device):
     return out
 
 
+def dump_outputs(out_dir, stats):
+    """What a caller of the timed path receives: train_one_epoch_vl returns the loop's meters averaged over the timed steps (the losses
+    of every step, the learning rate), written as out_dir/<meter>.npy, float64 of shape (1,).  With the same arguments these repeat from
+    run to run up to rounding (3e-5 relative or less after 20 + 5 steps at batch 256).  The model it trains in place does not: the backward sums stage-1
+    dK / dV and the embedding gradients with fp32 atomics before their bf16 casts, so a gradient repeats only to about 1e-2
+    (tests/test_fullsize_gpu.py, repeat-step test), and AdamW turns the rounding noise of a zero-expectation gradient (the key half of
+    each kv bias) into steps of +-lr -- neither is a function of the inputs that two runs or two builds can be compared on."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k in sorted(stats):
+        np.save(os.path.join(out_dir, k + ".npy"), np.array([stats[k]], dtype=np.float64))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks as CHILD processes of this one, which has not touched the GPU
     (no HIP call, no torch.cuda.is_available(); a process that has must never exec another program on this pool), the way the
@@ -404,6 +425,9 @@ def main():
     ap.add_argument("--model", default="pvlt_tiny")
     ap.add_argument("--task", default="pretrain", choices=["pretrain", "finetune"],
                     help="pretrain = {mlm,itm,t2i} (BASELINE configs 2-4); finetune = {cls} only (config 5, dws_mvlt_ft_exp48)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the meters train_one_epoch_vl returned as DIR/<meter>.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="also measure the blocks-only time, roofline launches, step traffic, BASELINE configurations #4 / #5 "
+                                                        "and the CPU baseline (each --no-* below drops one of them again)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the isolated roofline launches (whole-step counter passes: tools/step_traffic.sh)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of BASELINE configurations #4 / #5 behind the headline")
@@ -473,14 +497,17 @@ def main():
         per_rank = t.tolist()
         dt = max(per_rank)
     pairs_s = B * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, stats)
 
-    # blocks-only GPU time (SRAttention + MLP Blocks incl. their LayerNorms): two more iterations with HIP events around the
-    # Block kernels of every stage, forward and backward, outside the timed region
-    core._block_events = []
-    epoch(2, 2)
-    torch.cuda.synchronize()
-    ev, core._block_events = core._block_events, None
-    blocks_ms = sum(a.elapsed_time(b) for a, b in zip(ev[0::2], ev[1::2])) / 2.0
+    if args.full:
+        # blocks-only GPU time (SRAttention + MLP Blocks incl. their LayerNorms): two more iterations with HIP events around the
+        # Block kernels of every stage, forward and backward, outside the timed region
+        core._block_events = []
+        epoch(2, 2)
+        torch.cuda.synchronize()
+        ev, core._block_events = core._block_events, None
+        blocks_ms = sum(a.elapsed_time(b) for a, b in zip(ev[0::2], ev[1::2])) / 2.0
 
     if rank == 0:
         ms_step = 1e3 * dt / args.steps
@@ -515,13 +542,15 @@ def main():
                 "step_tflops_executed": round(per_gpu * executed / 1e12, 1),
                 "mfma_frac_reference_equivalent": round(per_gpu * FLOP_PER_PAIR_TRAIN / 1e12 / PEAK_BF16_TFLOPS, 4),
                 "mfma_frac_executed": round(per_gpu * executed / 1e12 / PEAK_BF16_TFLOPS, 4),
-                "blocks_only": {"what": "SRAttention + MLP Blocks (LN1, q, sr, kv, attention, proj, LN2, fc1, GELU, fc2; fwd + bwd): "
-                                        "3 x 8.003 GFLOP/pair over the GPU time between HIP events around the Block kernels",
-                                "ms_per_step": round(blocks_ms, 3),
-                                "tflops": round(3 * FWD_BLOCKS * B / (blocks_ms * 1e-3) / 1e12, 1),
-                                "mfma_frac": round(3 * FWD_BLOCKS * B / (blocks_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
-                                "target": 0.40},
             }
+        if args.full and args.model == "pvlt_tiny" and args.img == 256 and args.task == "pretrain":
+            line["flops"]["blocks_only"] = {
+                "what": "SRAttention + MLP Blocks (LN1, q, sr, kv, attention, proj, LN2, fc1, GELU, fc2; fwd + bwd): "
+                        "3 x 8.003 GFLOP/pair over the GPU time between HIP events around the Block kernels",
+                "ms_per_step": round(blocks_ms, 3),
+                "tflops": round(3 * FWD_BLOCKS * B / (blocks_ms * 1e-3) / 1e12, 1),
+                "mfma_frac": round(3 * FWD_BLOCKS * B / (blocks_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4),
+                "target": 0.40}
             if not args.no_roofline:
                 line["roofline"] = time_dominant_kernel(core, B, device, ms_step)
             gb, src = step_traffic()
@@ -529,11 +558,11 @@ def main():
                             "hbm_gb_per_step": gb, "hbm_tb_per_s": round(gb / ms_step, 2) if gb else None, "hbm_source": src}
             if world == 1 and B == 256 and not args.no_other_configs and not args.no_roofline:
                 line["other_configs"] = other_configs(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if use_pg:
-        dist.barrier()                                    # rank 0 is still timing its roofline launches: leave together
+        dist.barrier()                                    # rank 0 may still be timing its roofline launches: leave together
         dist.destroy_process_group()
 
 

@@ -221,3 +221,38 @@ def test_full_batch_gradients_equal_the_mean_of_its_chunks(parity, heads, lt, va
             continue
         worst = max(worst, (((g_q[k] / nchunk) - v).norm().item() / n, k))
     assert parity(f"{tag}/gradients vs mean of {nchunk} chunks, worst parameter ({worst[1]})", worst[0], gtol), worst
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs_every_run(tmp_path):
+    """`python bench.py --dump-outputs DIR` without --full: ONE JSON line with the contract's fields for exactly --steps timed steps, none of the
+    figures that --full adds, and in DIR the meters train_one_epoch_vl returned (the losses averaged over the timed steps, the learning rate);
+    a second run with the same arguments, at the bench's own batch, writes the same values up to rounding (same seeded inputs, same masks,
+    same computation)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    from mvlt_amd.engine import LOSS_KEYS
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    outs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, bench.__file__, "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "pairs/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert not {"roofline", "step", "other_configs", "cpu_baseline"} & set(out) and "blocks_only" not in out["flops"]
+    names = sorted(k + ".npy" for k in (*LOSS_KEYS, "lr"))
+    assert sorted(os.listdir(tmp_path / "a")) == names == sorted(os.listdir(tmp_path / "b"))
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and a.shape == (1,) and np.isfinite(a).all(), n
+        # measured at the bench's batch (256): <= 3e-5 relative after 20 + 5 steps (fp32 atomic order in the backward, carried by AdamW)
+        assert abs(a[0] - b[0]) <= 2e-4 * abs(b[0]) + 1e-7, (n, a[0], b[0])
+    assert abs(float(np.load(tmp_path / "a" / "total_loss.npy")[0]) - out["config"]["epoch_avg_loss"]) < 1e-3
+    assert float(np.load(tmp_path / "a" / "loss_mlm.npy")[0]) > 0 and float(np.load(tmp_path / "a" / "loss_t2i.npy")[0]) > 0

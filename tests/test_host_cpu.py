@@ -551,6 +551,20 @@ def test_bench_self_launch_refuses_more_ranks_than_gpus():
     assert r.returncode == 2 and "--gpus 64" in r.stderr, (r.returncode, r.stderr[-500:])
 
 
+def test_bench_dump_outputs_writes_the_meters_the_loop_returned(tmp_path):
+    """bench.dump_outputs (`bench.py --dump-outputs DIR`): every meter train_one_epoch_vl returned as DIR/<meter>.npy, float64 of shape (1,),
+    its value exactly, and nothing else."""
+    import numpy as np
+    import bench
+    stats = {"total_loss": 11.884671401977539, "loss_mlm": 9.21, "loss_itm": 0.885, "loss_sup_cls": 0.0, "loss_sub_cls": 0.0, "loss_t2i": 1.789,
+             "lr": 1.25e-4}
+    bench.dump_outputs(str(tmp_path / "d"), stats)
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(k + ".npy" for k in stats)
+    for k, v in stats.items():
+        a = np.load(tmp_path / "d" / (k + ".npy"))
+        assert a.dtype == np.float64 and a.shape == (1,) and a[0] == v, k
+
+
 def test_gelu_table_matches_exact_erf_gelu_and_its_generator():
     """csrc/gelu_lut.inc (the activation table of the fused-MLP weight-gradient kernels) holds { Phi(v) - 1/2, GELU'(v) - 1/2 } of the exact-erf
     GELU (reference libs/pvlt.py:62 nn.GELU) at every bf16 value 2^-9 <= v <= 8, and is what tools/gen_gelu_lut.py writes."""

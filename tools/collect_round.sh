@@ -6,8 +6,10 @@ set -u
 tag=${1:-r02}
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${tag}_bench_n1.json 2> gpurun_out/${tag}_bench_n1.err
-cut -c1-300 gpurun_out/${tag}_bench_n1.json
+res=${RESULTS:-results}                     # folder of the bench line (<tag>_bench_n1.json / .err)
+mkdir -p "$res"
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$res/${tag}_bench_n1.json" 2> "$res/${tag}_bench_n1.err"
+cut -c1-300 "$res/${tag}_bench_n1.json"
 bash tools/profile_bench.sh $tag --steps 6 --warmup 3 > /dev/null 2>&1
 cp gpurun_out/kernel_stats_$tag.csv gpurun_out/${tag}_kernel_stats.csv 2>/dev/null
 python3 tools/step_launches.py gpurun_out/prof_$tag/trace_kernel_trace.csv > gpurun_out/${tag}_step_launches.txt 2>&1

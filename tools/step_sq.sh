@@ -6,7 +6,7 @@ tag=${1:-r06}
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 out=gpurun_out/pmcstep_${tag}_SQ; rm -rf "$out"; mkdir -p "$out"
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES SQ_BUSY_CYCLES --kernel-trace --output-format csv -d "$out" -o p -- python3 bench.py --steps 4 --warmup 0 --no-cpu-baseline --no-roofline --no-other-configs > "$out/stdout.txt" 2> "$out/stderr.txt"
+rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVES SQ_BUSY_CYCLES --kernel-trace --output-format csv -d "$out" -o p -- python3 bench.py --full --steps 4 --warmup 0 --no-cpu-baseline --no-roofline --no-other-configs > "$out/stdout.txt" 2> "$out/stderr.txt"
 python3 tools/step_sq.py "$out" > gpurun_out/${tag}_step_sq.csv
 head -5 gpurun_out/${tag}_step_sq.csv
 rm -rf "$out"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """HBM bytes per kernel over whole training steps: two rocprofv3 passes (FETCH_SIZE, WRITE_SIZE, each with --kernel-trace only) over
-`bench.py --steps S --warmup 0 --no-cpu-baseline`, joined per kernel name.
+`bench.py --full --steps S --warmup 0 --no-cpu-baseline`, joined per kernel name.
     python3 tools/step_traffic.py <dir of FETCH_SIZE pass> <dir of WRITE_SIZE pass> [steps]   -> table on stdout (steps = AdamW launches seen)
 read bytes = 2 x FETCH_SIZE KiB (gfx950 half-count correction, MI355X_MICROARCH.md), written = WRITE_SIZE KiB."""
 import csv, glob, os, re, sys
