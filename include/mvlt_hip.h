@@ -26,8 +26,9 @@ extern "C" {
  *   3 (round 5): mvlt_gemm_tn_args.partials / partials_bytes; mvlt_last_kernel()
  *   4: mvlt_weight_prep blk_desc      5: mvlt_gemm_tn_args.defer_fold, mvlt_tn_fold_flush(), mvlt_tn_fold_discard()
  *   6 (round 6): mvlt_tn_fold_flush(partials, stream) / mvlt_tn_fold_discard(partials): the pending-fold table is kept per scratch (= per owner);
- *                mvlt_sr_attention_bwd_chunks(); mvlt_gemm_tn_args.c_overwrite; mvlt_mlp_args.partials / partials_bytes / defer_fold */
-#define MVLT_ABI_VERSION 6
+ *                mvlt_sr_attention_bwd_chunks(); mvlt_gemm_tn_args.c_overwrite; mvlt_mlp_args.partials / partials_bytes / defer_fold
+ *   7: mvlt_sr_attention_fwd_streamed() / mvlt_sr_attention_bwd_streamed(); the SR-attention entry points take any number of keys */
+#define MVLT_ABI_VERSION 7
 const char* mvlt_last_error(void);
 int mvlt_abi_version(void);
 /* the kernel instantiation the library launched last on the calling thread, as the HIP runtime names it, demangled (e.g. "void (anonymous
@@ -196,8 +197,9 @@ int mvlt_fold_copies(float* arena, int copies, long stride, const int* dst_index
 int mvlt_batch_sum(const void* in, float* out, int B, int R, int C, long batch_stride_rows, int ld, int dtype,
                    float* acc2 /* nullable: rows r >= split are ADDED to acc2[(r - split), :] instead of stored to out (text_pos_embed's gradient) */, int split, void* stream);
 
-/* Spatial-reduction attention core: O = softmax(Q K^T * scale) V per (batch, head), head_dim = 64,
- * M <= 320 keys (whole K/V of a head stays in LDS; single-pass softmax).  No mask (reference
+/* Spatial-reduction attention core: O = softmax(Q K^T * scale) V per (batch, head), head_dim = 64, any number M of keys.
+ * Up to 320 keys (bf16) / 288 keys (fp32) the whole K/V of a head stays in LDS; beyond, the keys stream through LDS in blocks
+ * (online softmax; mvlt_sr_attention_fwd_streamed below).  No mask (reference
  * libs/pvlt.py:113-117 applies none).  Q: (B,N,ldq) with head h at columns [64h,64h+64); K,V: (B,M,ldkv)
  * rows, head h at columns k_off+64h / v_off+64h of the kv buffer; O like Q.  lse[B,H,N] fp32 saved for bwd.
  * lse = ref * scale + log(sum of exp((s - ref) * scale)) where ref is a row maximum of the scores (bf16, M <= 192: the maximum over the
@@ -230,8 +232,15 @@ typedef struct mvlt_attn_bwd_args {
 int mvlt_sr_attention_bwd(const mvlt_attn_bwd_args* args, void* stream);
 /* number of query chunks per (batch, head) the backward would split an fp32-dKV launch of this shape into (dtype: MVLT_DT_*): 1 = every dK / dV element is
  * stored exactly once -- the caller may then hand a bf16 dKV (dkv_dtype 0) and skip the zero fill and the cast; > 1 = the chunks meet in fp32 atomics on a
- * caller-zeroed buffer.  Cost model in csrc/attention.hip (whole rounds of the chip x query tiles + atomics), fitted in round 6 (ABI 6). */
+ * caller-zeroed buffer.  Cost model in csrc/attention.hip (whole rounds of the chip x query tiles + atomics), fitted in round 6 (ABI 6).
+ * Past the LDS-resident range (bf16 M > 320, fp32 M > 288) the chunks are those of the streamed backward: ceil(N / 128) -- a bf16 dKV then
+ * needs N <= 128 and is refused (MVLT_ERR_ARG) otherwise. */
 int mvlt_sr_attention_bwd_chunks(int B, int H, int N, int M, int dtype);
+/* The key-streamed kernels at ANY M (the two entry points above route to them only past the resident range; these always do -- for tests
+ * and measurements against the resident kernels).  Same argument structs and contracts; the backward splits the queries of a (batch, head)
+ * into chunks of 128 (fp32 atomics into the caller-zeroed dKV when there are several; a bf16 dKV needs one chunk, N <= 128). */
+int mvlt_sr_attention_fwd_streamed(const mvlt_attn_args* args, void* stream);
+int mvlt_sr_attention_bwd_streamed(const mvlt_attn_bwd_args* args, void* stream);
 
 /* ---- HBM-bound helpers (mvlt_amd/csrc/elementwise.hip) ------------------------------------------------------- */
 

@@ -167,6 +167,28 @@ def sr_attention_bwd(Q, KV, O, dO, lse, dQ, dKV, B, H, N, M, ldq, ldkv, ldo, ldd
     return dQ, dKV
 
 
+L.lib.mvlt_sr_attention_fwd_streamed.argtypes = [C.POINTER(L.AttnArgs), C.c_void_p]
+L.lib.mvlt_sr_attention_bwd_streamed.argtypes = [C.POINTER(L.AttnBwdArgs), C.c_void_p]
+
+
+def sr_attention_fwd_streamed(Q, KV, O, lse, B, H, N, M, ldq, ldkv, ldo, k_off, v_off, scale):
+    """sr_attention_fwd on the key-streamed kernel at any M (sr_attention_fwd takes it only past the LDS-resident range)"""
+    assert Q.dtype == KV.dtype == O.dtype and Q.dtype in DT
+    a = L.AttnArgs(ptr(Q), ptr(KV), ptr(O), ptr(lse), B, H, N, M, ldq, ldkv, ldo, k_off, v_off, scale, DT[Q.dtype])
+    check(L.lib.mvlt_sr_attention_fwd_streamed(C.byref(a), stream_ptr()), "mvlt_sr_attention_fwd_streamed")
+    return O
+
+
+def sr_attention_bwd_streamed(Q, KV, O, dO, lse, dQ, dKV, B, H, N, M, ldq, ldkv, ldo, lddkv, k_off, v_off, scale):
+    """sr_attention_bwd on the key-streamed kernel at any M: chunks of 128 queries, fp32 atomics into a zeroed fp32 dKV when there are
+    several; a bf16 dKV needs N <= 128"""
+    assert dKV.dtype == torch.float32 or (dKV.dtype == torch.bfloat16 and Q.dtype == torch.bfloat16)
+    a = L.AttnBwdArgs(ptr(Q), ptr(KV), ptr(O), ptr(dO), ptr(lse), ptr(dQ), ptr(dKV), B, H, N, M,
+                      ldq, ldkv, ldo, lddkv, k_off, v_off, scale, DT[Q.dtype], DT[dKV.dtype])
+    check(L.lib.mvlt_sr_attention_bwd_streamed(C.byref(a), stream_ptr()), "mvlt_sr_attention_bwd_streamed")
+    return dQ, dKV
+
+
 # ------------------------------------------------------------------ helpers of csrc/elementwise.hip
 _vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
 L.lib.mvlt_bert_embed_fwd.argtypes = [_vp] * 7 + [_f, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]

@@ -144,6 +144,13 @@ class TrunkStep:
         HW = side * side
         pe = (param[:, 1:] if i == 3 else param)[0]                 # (grid*grid, C) rows of the flat buffer; stage 4 skips the cls slot
         if HW == m.grids[0] ** 2:          # reference libs/pvlt.py:292 compares with stage-1's constructor grid
+            if side != m.grids[i]:
+                # a later stage whose grid has stage 1's constructor patch count (448 px at the default 224: stage 2 is 56 x 56) gets its
+                # embedding unresized there, and the reference's `x + pos_embed` fails on the shapes; refuse the same way instead of reading
+                # side * side rows of a grids[i]^2-row parameter
+                raise RuntimeError(f"stage {i + 1}: a {side}x{side} token grid gets the {m.grids[i]}x{m.grids[i]} position embedding unresized "
+                                   f"(reference libs/pvlt.py:292 compares every stage with stage 1's {m.grids[0] ** 2} patches): the reference "
+                                   f"model cannot run this input size either")
             return pe
         pre = getattr(self, "_pos_pre", None)
         if pre is not None and i in pre:
