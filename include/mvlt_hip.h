@@ -45,7 +45,8 @@ int mvlt_sizeof(const char* name);
  *          logical row m = (b, oi, oj), logical column = (di*r + dj) * c_seg + c,
  *          phys_row = b*tokens_in + (oi*r+di)*w_in + (oj*r+dj).  This is nn.Conv2d(kernel=stride=r) on
  *          token-major data (reference libs/pvlt.py:92,104 Attention.sr and :162,168 PatchEmbed.proj);
- *          the conv weight is used as [out][di][dj][c].
+ *          the conv weight is used as [out][di][dj][c].  The grid need not be square: its height is hw_out / w_out output
+ *          rows (w_in = r * w_out).
  *  mode 2: 3x3 / stride 1 / zero-padded neighbourhood gather over an h_in x w_in pixel grid of a (B, tokens_in, c_seg)
  *          buffer (hw_out = h_in*w_in, w_out = w_in): logical row m = (b, y, x), logical column = (dy*3+dx)*c_seg + c,
  *          phys_row = b*tokens_in + (y+dy-1)*w_in + (x+dx-1), zero outside the grid.  This is nn.Conv2d(3, padding=1)
@@ -257,7 +258,7 @@ int mvlt_bert_embed_bwd(const void* dy, const long* ids, const float* word, cons
                         int rows, int T, int hidden, int dtype, void* stream);
 
 /* out[(b,oi,oj), (c,di,dj)] = img[b,c,oi*k+di,oj*k+dj]: the stage-1 PatchEmbed conv (reference libs/pvlt.py:162,168,
- * kernel=stride=4 on the NCHW fp32 image) becomes a K = 3*4*4 = 48 GEMM over this matrix. */
+ * kernel=stride=4 on the NCHW fp32 image) becomes a K = 3*4*4 = 48 GEMM over this matrix.  H and W are independent (multiples of k). */
 int mvlt_patchify(const float* img, void* out, int B, int Cin, int H, int W, int k, int dtype, void* stream);
 
 /* Masked-index selection (bit-exact): idx[0..*count) = ascending p with labels[p] != ignore_index.  This is the row
@@ -267,7 +268,8 @@ int mvlt_masked_select(const long* labels, int n, long ignore_index, int* idx, i
 /* Bilinear resize (align_corners=False, PyTorch index rule) of a token-major fp32 map in[Hin*Win, C] -> out[Hout*Wout, C]:
  * F.interpolate on the learned position embeddings, reference libs/pvlt.py:291-297 (`_get_pos_embed`).  adjoint != 0: `in` is
  * the gradient w.r.t. the resized [Hout*Wout, C] map and is ACCUMULATED (atomics) into out[Hin*Win, C], the gradient of the
- * source map. */
+ * source map.  Source and target grids are independent: the model resizes its square constructor grid to the h x w token grid
+ * of a rectangular input. */
 int mvlt_resize_bilinear_tokens(const float* in, int ld_in, float* out, int ld_out, int Hin, int Win, int Hout, int Wout, int C, int adjoint,
                                 void* stream);
 /* up to four of them in one launch (host arrays of `count` entries each): the position embeddings of the four stages, and their adjoints */
@@ -288,7 +290,7 @@ int mvlt_loss_compose(const float* const* losses, const float* weights, float* o
  *
  * mvlt_grid_mask_flags: flags[b, gh*gw] (1 = masked patch).  mode 0: exactly num_mask patches, uniformly.  mode 1: the
  *   reference generator `generate_grid_mask` (fashion_gen.py:225-254): one shuffle of [0]*(P-num_mask)+[1]*num_mask, then patch
- *   row i re-shuffles the window shuffled[i : i+gw].  At most 4096 patches per sample.
+ *   row i re-shuffles the window shuffled[i : i+gw].  At most 4096 patches per sample; gh and gw are independent.
  * mvlt_grid_mask_apply: masked[b,c,y,x] = flags[b, y/patch, x/patch] ? fill : image[b,c,y,x] on NCHW fp32 -- the
  *   `image.clone().masked_fill_(mask, 1e-6)` of fashion_gen.py:176 (fill = 1e-6, patch = 16).
  * mvlt_token_mask: `random_masking_features` (fashion_gen.py:383-409) on token ids: positions t >= 1 whose id is not
@@ -447,7 +449,7 @@ int mvlt_ew_mul(float* out, int ldo, const void* a, int lda, const void* b, int 
  * (the three-way feature product of reference libs/vl_heads.py:152) */
 int mvlt_ew_mul3_bwd(const void* dy /* fp32 or bf16 (dy_dtype) */, int lddy, const void* a, const void* b, const void* c, int ld, int in_dtype /* 1 fp32, 2 fp16 */,
                      void* da, void* db, void* dc /* dy's dtype */, long M, int C, int dy_dtype, void* stream);
-/* bilinear resize by an integer factor, align_corners=True.  x fp32 [B,H,W,C] (row stride ldx) -> [B,sH,sW,C] (bf16/fp32,
+/* bilinear resize by an integer factor, align_corners=True (H and W independent).  x fp32 [B,H,W,C] (row stride ldx) -> [B,sH,sW,C] (bf16/fp32,
  * row stride ldo) or NCHW fp32 [B,C,sH,sW]; bwd is the exact adjoint in gather form (no atomics); its dx is fp32 (dx_dtype 1) or,
  * behind the NCHW upsample only, bf16 (dx_dtype 0: the [pixels][8]-padded operand of the score conv's gradient GEMMs). */
 int mvlt_upsample_fwd(const float* x, int ldx, int B, int H, int W, int C, int scale, void* out, int ldo, int out_dtype, int nchw, void* stream);

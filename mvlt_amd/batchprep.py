@@ -32,9 +32,12 @@ class DeviceBatchPrep:
         self.sample = 0                           # running sample id: sample b of a call is self.sample + b
 
     def __call__(self, image, ori_input_ids, sample0=None, select=True):
-        """image (B,3,S,S) fp32 and ori_input_ids (B,T) int64 on the device -> dict(masked_images, patch_flags, input_ids,
-        mlm_labels[, mlm_positions_buf, mlm_count_dev]); kernels go to torch's current stream."""
+        """image (B,3,H,W) fp32 (H and W multiples of the 16-pixel patch, not necessarily equal) and ori_input_ids (B,T) int64 on the
+        device -> dict(masked_images (B,3,H,W), patch_flags (B,H/16,W/16), input_ids, mlm_labels[, mlm_positions_buf, mlm_count_dev]);
+        kernels go to torch's current stream."""
         assert image.is_cuda and image.dtype == torch.float32 and ori_input_ids.dtype == torch.int64
+        assert image.dim() == 4 and image.shape[2] % PATCH == 0 and image.shape[3] % PATCH == 0, \
+            f"image must be (B, 3, H, W) with H and W multiples of {PATCH}, got {tuple(image.shape)}"
         image, ori = image.contiguous(), ori_input_ids.contiguous()
         B, C, H, W = image.shape
         gh, gw = H // PATCH, W // PATCH

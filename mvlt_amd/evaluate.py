@@ -114,7 +114,7 @@ def rank_candidates(model, images, input_ids):
 @torch.no_grad()
 def evaluate_retrieval(data_loader, model, device, args, denominator=RETRIEVAL_DENOMINATOR):
     """acc@1/5/10 of the 101-candidate image<->text retrieval protocol.  Each loader item carries `images_101`
-    (1, 101, 3, S, S) and `ori_input_ids_101` (1, 101, T) (reference mcloader/fashion_gen.py:499-505, consumed at
+    (1, 101, 3, H, W) and `ori_input_ids_101` (1, 101, T) (reference mcloader/fashion_gen.py:499-505, consumed at
     engine_grid_masking.py:349-350).  `denominator=None` divides by the number of queries seen instead of the reference's 1000."""
     model.eval()
     logger = MetricLogger(delimiter="  ")

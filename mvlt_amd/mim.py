@@ -43,8 +43,8 @@ class MimStep:
         self.dev = x2.device
         self.x = (x2, x3, x4)                       # (B, N_i, C_i) stage outputs in the compute dtype, image tokens first
         self.B = x2.shape[0]
-        self.s1, self.s2, self.s3 = sides           # 32, 16, 8 at 256 px
-        self.M1, self.M2, self.M3 = (self.B * s * s for s in sides)
+        self.s1, self.s2, self.s3 = sides           # (h, w) grids of the three levels: 32 x 32, 16 x 16, 8 x 8 at 256 px
+        self.M1, self.M2, self.M3 = (self.B * h * w for h, w in sides)
         self.training = training
         self.need_grad = need_grad
         self.rec = {}                               # per conv: saved tensors for backward
@@ -54,7 +54,7 @@ class MimStep:
     def conv_bn(self, name, xin, ld_in, tokens_in, side, cin, cout, M):
         S, dev = self.S, self.dev
         p = f"t2i_head.{name}"
-        amap = conv3map(side, side, tokens_in, cin)
+        amap = conv3map(side[0], side[1], tokens_in, cin)
         bn = getattr(self.m.t2i_head, name)[1]
         if not self.training and not self.need_grad and not _NO_BN_FOLD:
             # inference: BatchNorm on its running statistics is an affine map per output channel -- folded into the conv (`norm` launches it
@@ -125,8 +125,8 @@ class MimStep:
     def up2(self, x32, ldx, side, C, out=None, ldo=None):
         B = self.B
         if out is None:
-            out, ldo = _e((B * 4 * side * side, C), self.dev, self.dt), C
-        ops.upsample_fwd(x32, ldx, B, side, side, C, 2, out, ldo)
+            out, ldo = _e((B * 4 * side[0] * side[1], C), self.dev, self.dt), C
+        ops.upsample_fwd(x32, ldx, B, side[0], side[1], C, 2, out, ldo)
         return out
 
     # ------------------------------------------------------------------ forward
@@ -145,39 +145,40 @@ class MimStep:
         r = self.conv_bn("reduction2", x3, C3, x3.shape[1], s2, C3, ch, M2); mid = _e((M2, ch), dev); self.norm(r, mid, ch)
         r = self.conv_bn("reduction3", x4, C4, x4.shape[1], s3, C4, ch, M3); high = _e((M3, ch), dev); self.norm(r, high, ch)
         uph = self.up2(high, ch, s3, ch)                                   # (B,16,16,64) operand dtype
+        HW1, HW2 = s1[0] * s1[1], s2[0] * s2[1]
         # a = cu1(up(high)) * mid            -> fp32 + operand copy into cat2[:, :64]
         cat2 = _e((M2, 2 * ch), dev, dt)
-        r = self.conv_bn("conv_upsample1", uph, ch, s2 * s2, s2, ch, ch, M2); cu1o = _e((M2, ch), dev); self.norm(r, cu1o, ch)
+        r = self.conv_bn("conv_upsample1", uph, ch, HW2, s2, ch, ch, M2); cu1o = _e((M2, ch), dev); self.norm(r, cu1o, ch)
         a = _e((M2, ch), dev)
         ops.ew_mul(a, ch, cu1o, ch, mid, ch, M=M2, Cdim=ch, out16=cat2, ld16=2 * ch)
-        r = self.conv_bn("conv_upsample4", uph, ch, s2 * s2, s2, ch, ch, M2); self.norm(r, y16=cat2[:, ch:], ld16=2 * ch)
-        r = self.conv_bn("conv_concat2", cat2, 2 * ch, s2 * s2, s2, 2 * ch, 2 * ch, M2); c = _e((M2, 2 * ch), dev); self.norm(r, c, 2 * ch)
+        r = self.conv_bn("conv_upsample4", uph, ch, HW2, s2, ch, ch, M2); self.norm(r, y16=cat2[:, ch:], ld16=2 * ch)
+        r = self.conv_bn("conv_concat2", cat2, 2 * ch, HW2, s2, 2 * ch, 2 * ch, M2); c = _e((M2, 2 * ch), dev); self.norm(r, c, 2 * ch)
         # b = cu2(up(mid)) * cu3(up(a)) * low -> fp32 + operand copy into cat3[:, :64]
         cat3 = _e((M1, 3 * ch), dev, dt)
         upm = self.up2(mid, ch, s2, ch)
-        r = self.conv_bn("conv_upsample2", upm, ch, s1 * s1, s1, ch, ch, M1); cu2o = _e((M1, ch), dev, f16); self.norm(r, cu2o, ch)
+        r = self.conv_bn("conv_upsample2", upm, ch, HW1, s1, ch, ch, M1); cu2o = _e((M1, ch), dev, f16); self.norm(r, cu2o, ch)
         upa = self.up2(a, ch, s2, ch)
-        r = self.conv_bn("conv_upsample3", upa, ch, s1 * s1, s1, ch, ch, M1); cu3o = _e((M1, ch), dev, f16); self.norm(r, cu3o, ch)
+        r = self.conv_bn("conv_upsample3", upa, ch, HW1, s1, ch, ch, M1); cu3o = _e((M1, ch), dev, f16); self.norm(r, cu3o, ch)
         ops.ew_mul(None, 0, cu2o, ch, cu3o, ch, low, ch, M=M1, Cdim=ch, out16=cat3, ld16=3 * ch)
         upc = self.up2(c, 2 * ch, s2, 2 * ch)
-        r = self.conv_bn("conv_upsample5", upc, 2 * ch, s1 * s1, s1, 2 * ch, 2 * ch, M1); self.norm(r, y16=cat3[:, ch:], ld16=3 * ch)
+        r = self.conv_bn("conv_upsample5", upc, 2 * ch, HW1, s1, 2 * ch, 2 * ch, M1); self.norm(r, y16=cat3[:, ch:], ld16=3 * ch)
         d16 = _e((M1, 3 * ch), dev, dt)
-        r = self.conv_bn("conv_concat3", cat3, 3 * ch, s1 * s1, s1, 3 * ch, 3 * ch, M1); self.norm(r, y16=d16, ld16=3 * ch)
+        r = self.conv_bn("conv_concat3", cat3, 3 * ch, HW1, s1, 3 * ch, 3 * ch, M1); self.norm(r, y16=d16, ld16=3 * ch)
         e16 = _e((M1, 3 * ch), dev, dt)
-        r = self.conv_bn("conv4", d16, 3 * ch, s1 * s1, s1, 3 * ch, 3 * ch, M1); self.norm(r, y16=e16, ld16=3 * ch)
+        r = self.conv_bn("conv4", d16, 3 * ch, HW1, s1, 3 * ch, 3 * ch, M1); self.norm(r, y16=e16, ld16=3 * ch)
         # score: conv1x1 (192 -> 3) + bias, then x8 bilinear to the image, written as NCHW fp32
         sc = _e((M1, 3), dev)
         ops.gemm_nt(e16, S.extra["t2i_head.score.0.weight::W"], sc, M1, 3, 3 * ch, 3 * ch, 3 * ch, 3, bias=S.master("t2i_head.score.0.bias"))
         if target is not None:
-            # training with the loss fused behind the decoder: SmoothL1 against the target image while interpolating, the (B, 3, S, S)
+            # training with the loss fused behind the decoder: SmoothL1 against the target image while interpolating, the (B, 3, H, W)
             # prediction is never written (and the backward recomputes it from the score map)
             acc = pool_zeros((1,), torch.float32, dev)
-            ops.upsample_l1_fwd(sc, 3, B, s1, s1, 3, 8, target, acc)
+            ops.upsample_l1_fwd(sc, 3, B, s1[0], s1[1], 3, 8, target, acc)
             out = (acc / target.numel()).reshape(())
             self.sc, self.target = sc, target
         else:
-            out = _e((B, 3, 8 * s1, 8 * s1), dev)
-            ops.upsample_fwd(sc, 3, B, s1, s1, 3, 8, out, 0, nchw=True)
+            out = _e((B, 3, 8 * s1[0], 8 * s1[1]), dev)
+            ops.upsample_fwd(sc, 3, B, s1[0], s1[1], 3, 8, out, 0, nchw=True)
         if self.nbt:
             torch._foreach_add_(self.nbt, 1)
             self.nbt = []
@@ -203,7 +204,7 @@ class MimStep:
         from .schedule import conv_wgrad
         conv_wgrad(S, p + ".0.weight", dz, r["xin"], M, cout, 9 * cin, cout, r["ld_in"], r["amap"], 9, cin)
         # dgrad: gather dz over the same grid with flipped taps
-        gmap = conv3map(r["side"], r["side"], r["side"] * r["side"], cout)
+        gmap = conv3map(r["side"][0], r["side"][1], r["side"][0] * r["side"][1], cout)
         if dx is None:
             dx, lddx = _e((M, cin), dev, dx_dtype), cin
         ops.gemm_nt(dz, S.extra[p + ".0.weight::F"], dx, M, cin, 9 * cout, cout, 9 * cout, lddx, a_map=gmap, c_map=dx_map,
@@ -218,11 +219,11 @@ class MimStep:
         # score head
         dsc_p = _z((M1, 8), dev, dt)                     # [pixels][3 -> 8] in the compute dtype: the operand of the two GEMMs below
         if getattr(self, "target", None) is not None:    # fused loss: dout is the scalar gradient of the loss
-            ops.upsample_l1_bwd(self.sc, 3, B, s1, s1, 3, 8, self.target, dout.reshape(1).float().contiguous(), dsc_p, 8)
+            ops.upsample_l1_bwd(self.sc, 3, B, s1[0], s1[1], 3, 8, self.target, dout.reshape(1).float().contiguous(), dsc_p, 8)
             self.sc = self.target = None
         else:
             dout = dout.contiguous().float()
-            ops.upsample_bwd(dout, 0, True, B, s1, s1, 3, 8, dsc_p, 8)
+            ops.upsample_bwd(dout, 0, True, B, s1[0], s1[1], 3, 8, dsc_p, 8)
         # weight gradient and, as the GEMM's column sum, the bias gradient (a torch sum over a [262144, 3] matrix took 92 us)
         ops.gemm_tn(dsc_p, k["e16"], S.grad("t2i_head.score.0.weight").view(3, 3 * ch), M1, 3, 3 * ch, 8, 3 * ch, 3 * ch,
                     colsum=S.grad("t2i_head.score.0.bias"))
@@ -235,7 +236,7 @@ class MimStep:
         dcat3 = self.bn_conv_bwd("conv_concat3", dd, 3 * ch, dx_dtype=gd)          # [:, :64] = db, [:, 64:] = d(cu5 out)
         dupc = self.bn_conv_bwd("conv_upsample5", dcat3[:, ch:], 3 * ch, dx_dtype=gd)
         dc = _e((M2, 2 * ch), dev)
-        ops.upsample_bwd(dupc, 2 * ch, False, B, s2, s2, 2 * ch, 2, dc, 2 * ch)
+        ops.upsample_bwd(dupc, 2 * ch, False, B, s2[0], s2[1], 2 * ch, 2, dc, 2 * ch)
         # b = cu2o * cu3o * low
         db = dcat3                                                                  # columns [0, 64), row stride 192
         dcu2o, dcu3o, dlow = _e((M1, ch), dev, gd), _e((M1, ch), dev, gd), _e((M1, ch), dev, gd)
@@ -243,10 +244,10 @@ class MimStep:
         # gradient of cat2 = [a | cu4 out]: starts with the path a -> up -> cu3
         dcat2 = _z((M2, 2 * ch), dev)
         dupa = self.bn_conv_bwd("conv_upsample3", dcu3o, ch, dx_dtype=gd)
-        ops.upsample_bwd(dupa, ch, False, B, s2, s2, ch, 2, dcat2, 2 * ch, accumulate=True)
+        ops.upsample_bwd(dupa, ch, False, B, s2[0], s2[1], ch, 2, dcat2, 2 * ch, accumulate=True)
         dupm = self.bn_conv_bwd("conv_upsample2", dcu2o, ch, dx_dtype=gd)
         dmid = _e((M2, ch), dev)
-        ops.upsample_bwd(dupm, ch, False, B, s2, s2, ch, 2, dmid, ch)
+        ops.upsample_bwd(dupm, ch, False, B, s2[0], s2[1], ch, 2, dmid, ch)
         self.bn_conv_bwd("conv_concat2", dc, 2 * ch, dx=dcat2, lddx=2 * ch, accumulate=True)
         duph = self.bn_conv_bwd("conv_upsample4", dcat2[:, ch:], 2 * ch)
         # a = cu1o * mid
@@ -255,7 +256,7 @@ class MimStep:
         ops.ew_mul(dmid, ch, dcat2, 2 * ch, k["cu1o"], ch, M=M2, Cdim=ch, accumulate=True)
         self.bn_conv_bwd("conv_upsample1", dcu1o, ch, dx=duph, lddx=ch, accumulate=True)
         dhigh = _e((M3, ch), dev)
-        ops.upsample_bwd(duph, ch, False, B, s3, s3, ch, 2, dhigh, ch)
+        ops.upsample_bwd(duph, ch, False, B, s3[0], s3[1], ch, 2, dhigh, ch)
         # reductions: gradients w.r.t. the image tokens of the stage outputs (text rows stay zero)
         grads = []
         for name, dy, x, side in (("reduction1", dlow, self.x[0], s1), ("reduction2", dmid, self.x[1], s2), ("reduction3", dhigh, self.x[2], s3)):
@@ -263,8 +264,8 @@ class MimStep:
                 dxs, ret = sink.take(x.shape, x.dtype, x.device)      # the heads' common buffer: image rows are this decoder's
             else:
                 dxs = ret = S.own(torch.empty_like(x))     # image rows are all written by the conv dgrad below;
-                dxs[:, side * side:].zero_()               # only the text rows need the explicit zeros
-            self.bn_conv_bwd(name, dy, ch, dx=dxs, lddx=x.shape[2], dx_map=rowmap(side * side, x.shape[1], 0))
+                dxs[:, side[0] * side[1]:].zero_()         # only the text rows need the explicit zeros
+            self.bn_conv_bwd(name, dy, ch, dx=dxs, lddx=x.shape[2], dx_map=rowmap(side[0] * side[1], x.shape[1], 0))
             grads.append(ret)
         self.rec, self.keep = {}, {}
         return grads
@@ -290,5 +291,5 @@ class _MimFn(torch.autograd.Function):
 
 
 def mim_head(model, x2, x3, x4, sides, need_grad, sink=None, target=None):
-    """-> t2i_logits (B, 3, S, S), or with `target` (fp32 NCHW image) the mean SmoothL1 loss against it as a 0-dim tensor"""
+    """sides: the (h, w) token grids of stages 2-4.  -> t2i_logits (B, 3, 8 h_2, 8 w_2), or with `target` (fp32 NCHW image) the mean SmoothL1 loss against it as a 0-dim tensor"""
     return _MimFn.apply(x2, x3, x4, model, sides, need_grad, sink, target)

@@ -264,14 +264,13 @@ class PyramidVisionLanguageTransformer(nn.Module):
         token buffers to the heads directly)."""
         if not x.is_cuda:
             raise RuntimeError("mvlt_amd PVLT runs on MI355X only (HIP kernels); there is no CPU path.")
-        from .schedule import run_trunk
+        from .schedule import run_trunk, stage_grids
         outs = run_trunk(self, x, y)
-        B, side = x.shape[0], x.shape[2] // self.patch_size
+        B = x.shape[0]
         img_feats, text_feats = [], []
-        for i, t in enumerate(outs):
-            s_i = side // (2 ** i)
-            img_feats.append(t[:, : s_i * s_i, :].reshape(B, s_i, s_i, -1).permute(0, 3, 1, 2).contiguous())
-            text_feats.append(t[:, s_i * s_i:, :])
+        for (h_i, w_i), t in zip(stage_grids(self, x.shape[2], x.shape[3]), outs):
+            img_feats.append(t[:, : h_i * w_i, :].reshape(B, h_i, w_i, -1).permute(0, 3, 1, 2).contiguous())
+            text_feats.append(t[:, h_i * w_i:, :])
         return img_feats, text_feats
 
 

@@ -67,6 +67,19 @@ def _step_rng(model):
     return torch.initial_seed(), model._rng_calls
 
 
+def check_input_size(model, Himg, Wimg):
+    """the reference's input rule: each side a multiple of patch_size * 8 = 32 (its patch embeddings halve the map three times and the MIM decoder's
+    x2 upsamples must meet the skip maps again); rectangles are fine (reference libs/pvlt.py:166-172,291-297)"""
+    unit = model.patch_size * 8
+    assert Himg % unit == 0 and Wimg % unit == 0, \
+        f"input size {Himg} x {Wimg} (H x W): each side should be divided by patch_size {unit} (rectangles are fine, as in the reference)"
+
+
+def stage_grids(model, Himg, Wimg):
+    """[(h_i, w_i)] token grids of the four stages for an Himg x Wimg input"""
+    return [(Himg // model.patch_size // (2 ** i), Wimg // model.patch_size // (2 ** i)) for i in range(4)]
+
+
 class Names:
     """parameter-name helpers"""
 
@@ -92,12 +105,11 @@ class TrunkStep:
         self.B = images.shape[0]
         assert images.shape[1] == model.in_chans
         Himg, Wimg = images.shape[2], images.shape[3]
-        assert Himg == Wimg, "square inputs only (the reference's pos-embed handling assumes them)"
-        assert Himg % (model.patch_size * 8) == 0, f"img_size {Himg} should be divided by patch_size {model.patch_size * 8}."
-        self.img = Himg
+        check_input_size(model, Himg, Wimg)
+        self.Himg, self.Wimg = Himg, Wimg
         self.T = ids.shape[1]
         assert self.T == model.T_num, "input_ids length must equal num_text_tokens"
-        self.side = [Himg // model.patch_size // (2 ** i) for i in range(4)]
+        self.grid = stage_grids(model, Himg, Wimg)       # (h_i, w_i) token grid of every stage
         self.saved = []          # per stage dict
         self.training = model.training
 
@@ -140,23 +152,23 @@ class TrunkStep:
     # ---- pos embed: learned for the constructor grid, bilinearly resized (align_corners=False) to this input's grid
     def _pos(self, i, param):
         m = self.m
-        side, C = self.side[i], m.dims[i]
-        HW = side * side
+        (h, w), C = self.grid[i], m.dims[i]
+        HW = h * w
         pe = (param[:, 1:] if i == 3 else param)[0]                 # (grid*grid, C) rows of the flat buffer; stage 4 skips the cls slot
-        if HW == m.grids[0] ** 2:          # reference libs/pvlt.py:292 compares with stage-1's constructor grid
-            if side != m.grids[i]:
+        if HW == m.grids[0] ** 2:          # reference libs/pvlt.py:292 compares the patch COUNT with stage-1's constructor grid
+            if HW != m.grids[i] ** 2:
                 # a later stage whose grid has stage 1's constructor patch count (448 px at the default 224: stage 2 is 56 x 56) gets its
                 # embedding unresized there, and the reference's `x + pos_embed` fails on the shapes; refuse the same way instead of reading
-                # side * side rows of a grids[i]^2-row parameter
-                raise RuntimeError(f"stage {i + 1}: a {side}x{side} token grid gets the {m.grids[i]}x{m.grids[i]} position embedding unresized "
+                # h * w rows of a grids[i]^2-row parameter
+                raise RuntimeError(f"stage {i + 1}: a {h}x{w} token grid gets the {m.grids[i]}x{m.grids[i]} position embedding unresized "
                                    f"(reference libs/pvlt.py:292 compares every stage with stage 1's {m.grids[0] ** 2} patches): the reference "
                                    f"model cannot run this input size either")
-            return pe
+            return pe          # (a non-square stage-1 grid of that count -- 392 x 8 at the default 224 -- adds the square embedding row for row, like the reference)
         pre = getattr(self, "_pos_pre", None)
         if pre is not None and i in pre:
             return pre[i]                      # resized by the one launch at the start of the forward pass (`_pos_prefetch`)
         out = _empty((HW, C), torch.float32, self.dev)
-        ops.resize_bilinear_tokens(pe, out, m.grids[i], m.grids[i], side, side, C)
+        ops.resize_bilinear_tokens(pe, out, m.grids[i], m.grids[i], h, w, C)
         return out
 
     def _pos_prefetch(self):
@@ -164,13 +176,13 @@ class TrunkStep:
         m = self.m
         jobs, self._pos_pre = [], {}
         for i in range(4):
-            side, C = self.side[i], m.dims[i]
-            if side * side == m.grids[0] ** 2:
+            (h, w), C = self.grid[i], m.dims[i]
+            if h * w == m.grids[0] ** 2:
                 continue
             param = self.f32(f"pos_embed{i+1}")
             pe = (param[:, 1:] if i == 3 else param)[0]
-            out = _empty((side * side, C), torch.float32, self.dev)
-            jobs.append((pe, out, m.grids[i], m.grids[i], side, side, C))
+            out = _empty((h * w, C), torch.float32, self.dev)
+            jobs.append((pe, out, m.grids[i], m.grids[i], h, w, C))
             self._pos_pre[i] = out
         if jobs and not _NO_POS_BATCH:
             ops.resize_bilinear_tokens_multi(jobs)
@@ -228,22 +240,22 @@ class TrunkStep:
     def _stage_forward(self, i, xp, blk_index):
         m, B, T, dt, dev = self.m, self.B, self.T, self.dt, self.dev
         C = m.dims[i]
-        side = self.side[i]
-        HW = side * side
+        h, w = self.grid[i]
+        HW = h * w
         N = HW + T
-        sv = dict(i=i, C=C, HW=HW, N=N, side=side)
+        sv = dict(i=i, C=C, HW=HW, N=N)
         pe, ten = f"patch_embed{i+1}.", f"text_embed{i+1}."
         # ---- patch embed: kernel==stride conv as GEMM, then LN(1e-5) + pos-embed written into x[:, :HW]
         pe_pre = _empty((B * HW, C), dt, dev)
         if i == 0:
             K = m.in_chans * m.patch_size ** 2
             P1 = _empty((B * HW, K), dt, dev)
-            ops.patchify(self.images, P1, B, m.in_chans, self.img, self.img, m.patch_size)
+            ops.patchify(self.images, P1, B, m.in_chans, self.Himg, self.Wimg, m.patch_size)
             ops.gemm_nt(P1, self.w(pe + "proj.weight"), pe_pre, B * HW, C, K, K, K, C, bias=self.f32(pe + "proj.bias"))
             sv["P1"] = P1
         else:
-            Cp, Np, sp = m.dims[i - 1], self.saved[i - 1]["N"], self.side[i - 1]
-            pm = patchmap(2, sp, Np, HW, side, Cp)
+            Cp, Np, wp = m.dims[i - 1], self.saved[i - 1]["N"], self.grid[i - 1][1]
+            pm = patchmap(2, wp, Np, HW, w, Cp)
             ops.gemm_nt(xp, self.wK(pe + "proj.weight"), pe_pre, B * HW, C, 4 * Cp, Cp, 4 * Cp, C, a_map=pm,
                         bias=self.f32(pe + "proj.bias"))
             sv["pm_in"] = pm
@@ -287,7 +299,7 @@ class TrunkStep:
         sv["x_out"] = x
         taps = getattr(m, "_taps", None)
         if taps is not None:            # tests: stage outputs in the reference's (img_feat NCHW, text_feat) form
-            taps[f"img_feat{i+1}"] = x[:, :HW].float().reshape(B, side, side, C).permute(0, 3, 1, 2)
+            taps[f"img_feat{i+1}"] = x[:, :HW].float().reshape(B, h, w, C).permute(0, 3, 1, 2)
             taps[f"text_feat{i+1}"] = x[:, HW:].float()
         self.saved.append(sv)
         return x, blk_index
@@ -295,8 +307,8 @@ class TrunkStep:
     def _block_forward(self, i, j, x, blk_index):
         m, B, T, dt, dev = self.m, self.B, self.T, self.dt, self.dev
         C, h, r, hid = m.dims[i], m.heads[i], m.sr[i], m.hid[i]
-        side = self.side[i]
-        HW = side * side
+        gh, gw = self.grid[i]
+        HW = gh * gw
         N = HW + T
         M = B * N
         p = Names.blk(i, j)
@@ -320,10 +332,9 @@ class TrunkStep:
         bs["q"] = q
         # k, v source: spatially reduced image tokens (conv r x r stride r + LN 1e-5) followed by the text tokens
         if r > 1:
-            sr_side = side // r
-            HWr = sr_side * sr_side
+            HWr = (gh // r) * (gw // r)
             Mk = HWr + T
-            pm = patchmap(r, side, N, HWr, sr_side, C)
+            pm = patchmap(r, gw, N, HWr, gw // r, C)
             sr_pre = _empty((B * HWr, C), dt, dev)
             ops.gemm_nt(xn1, self.wK(p + "attn.sr.weight"), sr_pre, B * HWr, C, r * r * C, C, r * r * C, C, a_map=pm,
                         bias=self.f32(p + "attn.sr.bias"))
@@ -440,7 +451,7 @@ class TrunkStep:
 
     def _stage_backward(self, i, sv, dx, into=None):
         m, B, T, dt, dev = self.m, self.B, self.T, self.dt, self.dev
-        C, HW, N, side = sv["C"], sv["HW"], sv["N"], sv["side"]
+        C, HW, N = sv["C"], sv["HW"], sv["N"]
         self._mark()
         for j in reversed(range(m.depths[i])):
             dx = self._block_backward(i, j, sv["blocks"][j], dx)
@@ -468,7 +479,7 @@ class TrunkStep:
             ops.gemm_nt(d_te, self.wT(ten + "0.weight"), d_emb, B * T, m.hidden, C, C, C, m.hidden)
             self._bert_backward(d_emb)
             return None
-        Cp, Np, HWp, sp = m.dims[i - 1], self.saved[i - 1]["N"], self.saved[i - 1]["HW"], self.side[i - 1]
+        Cp, Np, HWp = m.dims[i - 1], self.saved[i - 1]["N"], self.saved[i - 1]["HW"]
         xp = sv["x_in_prev"]
         pm = sv["pm_in"]
         # conv weight gradient: computed in the gather's [out][kh][kw][cin] order, accumulated at its [out][cin][kh][kw] place
@@ -482,18 +493,18 @@ class TrunkStep:
 
     def _pos_backward(self, i, dpos):
         m = self.m
-        side = self.side[i]
-        HW = side * side
+        h, w = self.grid[i]
+        HW = h * w
         gv = self.g(f"pos_embed{i+1}")
         gv = (gv[:, 1:] if i == 3 else gv)[0]
         if HW == m.grids[0] ** 2:
             gv.add_(dpos)
             return
         if _NO_POS_BATCH:
-            ops.resize_bilinear_tokens(dpos, gv, m.grids[i], m.grids[i], side, side, dpos.shape[1], adjoint=True)   # accumulates into G
+            ops.resize_bilinear_tokens(dpos, gv, m.grids[i], m.grids[i], h, w, dpos.shape[1], adjoint=True)   # accumulates into G
         else:
             # the adjoints of all stages leave in one launch at the end of the trunk's backward (`backward`): dpos stays alive in the list until then
-            self._pos_adj.append((dpos, gv, m.grids[i], m.grids[i], side, side, dpos.shape[1]))
+            self._pos_adj.append((dpos, gv, m.grids[i], m.grids[i], h, w, dpos.shape[1]))
 
     def _bert_backward(self, d_emb):
         m, B, T = self.m, self.B, self.T
@@ -508,8 +519,7 @@ class TrunkStep:
         """dx: gradient w.r.t. the block output (B,N,C), overwritten in place with the gradient w.r.t. its input."""
         m, B, T, dt, dev = self.m, self.B, self.T, self.dt, self.dev
         C, h, r, hid = m.dims[i], m.heads[i], m.sr[i], m.hid[i]
-        side = self.side[i]
-        HW = side * side
+        HW = self.grid[i][0] * self.grid[i][1]
         N = HW + T
         M = B * N
         p = Names.blk(i, j)
@@ -904,7 +914,7 @@ class _HostCount:
 
 def run_forward(model, images, ids, mlm_labels=None, mlm_positions=None, mlm_count=None, t2i_target=None):
     """mlm_labels: (B, T) int64 with -1 = not selected -> fused masked-row MLM head + loss (`mlm_loss`).
-    t2i_target: (B, 3, S, S) fp32 clean image -> the MIM decoder returns its SmoothL1 loss (`t2i_loss`) instead of `t2i_logits`
+    t2i_target: (B, 3, H, W) fp32 clean image -> the MIM decoder returns its SmoothL1 loss (`t2i_loss`) instead of `t2i_logits`
     (training: the image-sized prediction is never materialised, engine_grid_masking.py:99 is fused behind vl_heads.py:163-165).
     mlm_positions: optional precomputed selection (ascending flat indices, int32, on the device).
     mlm_count: optional number of selected positions as a host int (the engine counts on the host when the loader hands it
@@ -926,8 +936,8 @@ def run_forward(model, images, ids, mlm_labels=None, mlm_positions=None, mlm_cou
     x1, x2, x3, x4 = _TrunkFn.apply(model, images, ids, grad_on, *[p for _, p in S.fn_params])
     sink = _GradSink(S) if grad_on else None            # the heads' common gradient buffer for x4
     B = images.shape[0]
-    side4 = images.shape[2] // model.patch_size // 8
-    HW4 = side4 * side4
+    grids = stage_grids(model, images.shape[2], images.shape[3])
+    HW4 = grids[3][0] * grids[3][1]
     out = dict(mlm_logits=None, itm_logits=None, sup_cls_logits=None, sub_cls_logits=None, t2i_logits=None)
     if lt['mlm']:
         if mlm_labels is not None:
@@ -954,9 +964,9 @@ def run_forward(model, images, ids, mlm_labels=None, mlm_positions=None, mlm_cou
         from .mim import mim_head
         if grad_on and not model.training:
             raise NotImplementedError("MIM decoder backward with eval-mode BatchNorm is not scheduled (no reference config needs it)")
-        sides = tuple(images.shape[2] // model.patch_size // (2 ** i) for i in (1, 2, 3))
-        fuse_loss = (t2i_target is not None and t2i_target.dtype == torch.float32 and t2i_target.shape == (B, 3, 8 * sides[0], 8 * sides[0])
-                     and ops.upsample_l1_ok(sides[0], 8) and not _NO_T2I_FUSE)
+        sides = tuple(grids[1:])                      # the (h, w) grids of the three pyramid levels the decoder reads
+        fuse_loss = (t2i_target is not None and t2i_target.dtype == torch.float32 and t2i_target.shape == (B, 3, 8 * sides[0][0], 8 * sides[0][1])
+                     and ops.upsample_l1_ok(sides[0][1], 8) and not _NO_T2I_FUSE)
         if fuse_loss:
             out["t2i_loss"] = mim_head(model, x2, x3, x4, sides, grad_on, sink, t2i_target.contiguous())
         else:
