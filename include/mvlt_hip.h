@@ -120,11 +120,11 @@ typedef struct mvlt_gemm_tn_args {
   /* optional scratch for split reductions WITHOUT atomics (round 5): every m-split stores its output tile to partials[split][N1][N2] in bf16 and an ordered fold
    * (tn_fold_kernel) adds the splits to C -- deterministic (bit-identical from launch to launch), one bf16 rounding per split's partial sum (max-norm error 2e-3 of the
    * gradient instead of 1e-5).  Taken by (a) outputs of 16 .. 64 whole 256 x 256 tiles with M a multiple of 64 (the fc1 / fc2 weight gradients of a stage-4 block, 2048 x 512
-   * over 49152 rows: 8-wave / 8-phase TN kernel, 114 against 132 us), (b) the 128-wide kernel when >= 8 m-splits meet on an output of >= 65536 elements (q / proj / kv
-   * weight gradients of stages 3-4: 40-45 against 53-56 us), (c) the conv3x3 weight-gradient kernel with >= 4 m-splits; bf16 operands, plain rows (b_map mode 2 for (c)),
+   * over 49152 rows: 8-wave / 8-phase TN kernel, 114 against 132 us), (b) the 128-wide kernel when >= 8 m-splits meet on an output of >= 16384 elements (q / proj / kv
+   * weight gradients of stages 3-4: 40-45 against 53-56 us; text_embed1's 64 x 768 gradient), (c) the conv3x3 weight-gradient kernel with >= 4 m-splits; bf16 operands, plain rows (b_map mode 2 for (c)),
    * trans_c == 0, c_taps <= 1.  A launch whose splits x N1 x N2 x 2 bytes exceed partials_bytes, or partials == NULL, takes the atomic path.  Sizing: the largest single
    * launch of the BASELINE configurations needs 37 MiB (56 splits x 192 x 1728); with defer_fold several launches SHARE the scratch -- each takes the next free region, the
-   * library folds by itself when the next one does not fit -- so the host side holds 256 MiB per parameter store (MVLT_TN_SCRATCH_MIB): ~4 fold launches per step. */
+   * library folds by itself when the next one does not fit -- so the host side holds 256 MiB per parameter store: ~4 fold launches per step. */
   void* partials; long partials_bytes;
   /* 1: leave this launch's partial tiles in the scratch (each deferring launch takes the next free region of it) and fold them together with the next ones -- up to 32 per fold
    * launch; the library folds by itself when its table or the scratch is full or when a non-deferring launch needs the scratch, and when the caller says

@@ -1131,7 +1131,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_bwd_dma_kernel(
 // cost) x 3.2 us, + chunks x groups x M x 128 atomics at 0.5 per ns when there is more than one chunk.  `slots` = workgroups the chip holds at once (two per CU for
 // the four-wave bf16 instantiations, one otherwise).  It reproduces ceil(512 / groups) on every 256-px shape of the BASELINE configurations.
 inline int attn_bwd_chunks(int groups, int N, int M, int slots, bool one_chunk_only, int* q_per_wg) {
-  static const int force = getenv("MVLT_ATTN_BWD_NQ") ? atoi(getenv("MVLT_ATTN_BWD_NQ")) : 0;      // measurement switch (tools/ubench_attn.py)
   int best_nq = 1;
   double best = -1.0;
   const int max_nq = one_chunk_only ? 1 : min(128, max(1, (N + 63) / 64));       // at least two query tiles per chunk
@@ -1141,7 +1140,6 @@ inline int attn_bwd_chunks(int groups, int N, int M, int slots, bool one_chunk_o
     const long rounds = ((long)groups * nq + slots - 1) / slots;
     double cost = (double)rounds * (qpw / 32 + 2) * 3.2;
     if (nq > 1) cost += (double)nq * groups * M * 128.0 / 500.0 * 1e-3;
-    if (force > 0 && !one_chunk_only) cost = nq == force ? 0.0 : 1.0;
     if (best < 0.0 || cost < best) { best = cost; best_nq = nq; }
   }
   *q_per_wg = ((N + best_nq - 1) / best_nq + 31) / 32 * 32;

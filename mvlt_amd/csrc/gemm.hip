@@ -1710,7 +1710,7 @@ template <int W> int launch_conv3_wgrad(const mvlt_gemm_tn_args& a, hipStream_t 
   const int n_o = a.N1 / 64, n_c = a.b_map.c_seg / 64, ntiles = a.M / 64;
   // every split flushes its whole 64 x 576 block with fp32 atomics: at least 16 k-tiles of work per flush, about two workgroups per
   // CU when the shape allows (262144 x 64 x 576: 640 splits of 7 tiles 108 us, 256 splits of 16 tiles measured below)
-  static const int min_tiles = getenv("MVLT_CONV_WGRAD_MINT") ? atoi(getenv("MVLT_CONV_WGRAD_MINT")) : 16;
+  constexpr int min_tiles = 16;
   int splits = (512 + n_o * n_c - 1) / (n_o * n_c);
   if (splits > ntiles / min_tiles) splits = ntiles / min_tiles;
   if (splits < 1) splits = 1;
@@ -1720,9 +1720,8 @@ template <int W> int launch_conv3_wgrad(const mvlt_gemm_tn_args& a, hipStream_t 
   splits = (ntiles + tps - 1) / tps;
   dim3 grid((unsigned)((splits >= 8 ? 8 * ((splits + 7) / 8) : splits) * n_o * n_c)), block(NTHREADS);
   mvlt_max_lds<(conv3_wgrad_kernel<W>)>();
-  // the caller's scratch takes the splits' blocks (bf16) and an ordered fold adds them to C: no atomics (MVLT_TN_P8=0 keeps them)
-  static const bool part_ok = !(getenv("MVLT_TN_P8") && atoi(getenv("MVLT_TN_P8")) == 0);
-  bf16* const part = (part_ok && a.partials && splits >= 4 && a.ldc % 4 == 0 && ((uintptr_t)a.C & 15) == 0 && lds >= (size_t)4 * 16 * (9 * 32 + 8) * 2)
+  // the caller's scratch takes the splits' blocks (bf16) and an ordered fold adds them to C: no atomics
+  bf16* const part = (a.partials && splits >= 4 && a.ldc % 4 == 0 && ((uintptr_t)a.C & 15) == 0 && lds >= (size_t)4 * 16 * (9 * 32 + 8) * 2)
                          ? fold_acquire(a, (long)splits * a.N1 * a.N2 * 2, s) : nullptr;
   MVLT_LAUNCH((conv3_wgrad_kernel<W>), grid, block, lds, s, a, tps, n_o, n_c, splits, part);
   if (part) fold_launch(a, part, splits, s);
@@ -2238,8 +2237,7 @@ template <int EPI, int HM, int HN0, int HN1, bool RAG = false> void launch_nt_p8
   constexpr int LDS_LOOP = 2 * (2 * (2 * HM * 16) + 64 * (HN0 + HN1)) * 128;
   constexpr int LDS_EPI = 8 * 32 * (16 * (HN0 + HN1) + 4) * 4;
   constexpr int LDS = LDS_LOOP > LDS_EPI ? LDS_LOOP : LDS_EPI;
-  static bool once = (hipFuncSetAttribute((const void*)gemm_nt_p8_kernel<EPI, HM, HN0, HN1, RAG>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess);
-  (void)once;
+  mvlt_max_lds<(gemm_nt_p8_kernel<EPI, HM, HN0, HN1, RAG>)>();
   const int tiles_m = (a.M + BMT - 1) / BMT, tiles_n = (a.N + BNT - 1) / BNT;
   dim3 grid((unsigned)(8 * ((tiles_m + 7) / 8) * tiles_n)), block(512);
   MVLT_LAUNCH((gemm_nt_p8_kernel<EPI, HM, HN0, HN1, RAG>), grid, block, LDS, s, a);
@@ -2873,11 +2871,11 @@ extern "C" int mvlt_gemm_nt(const mvlt_gemm_nt_args* a, void* stream) {
                "mvlt_gemm_nt: split_k needs bf16 operands, fp32 C (zeroed by the caller) and a plain epilogue (A may be gathered)");
   MVLT_REQUIRE(a->col_copies >= 0, "mvlt_gemm_nt: col_copies < 0");
   MVLT_REQUIRE(!a->r_fp32 || (a->R && a->R != a->C && a->dtype == 0 && a->out_dtype == 0 && a->act == 0 && !a->col_sum && !a->post_y && a->split_k <= 1 && a->c_map.mode == 0 &&
-                              a->N % 8 == 0 && a->ldc % 8 == 0 && (((uintptr_t)a->C | (uintptr_t)a->R) & 15) == 0 && a->M < (1 << 24) && !getenv("MVLT_NT_GENERIC_EPI")),
+                              a->N % 8 == 0 && a->ldc % 8 == 0 && (((uintptr_t)a->C | (uintptr_t)a->R) & 15) == 0 && a->M < (1 << 24)),
                "mvlt_gemm_nt: r_fp32 (fp32 residual beside a bf16 C) exists in the residual epilogue of the bf16 LDS-DMA kernels only (plain c_map, N % 8 == 0, 16-byte aligned C / R)");
   MVLT_REQUIRE(a->out_dtype >= 0 && a->out_dtype <= 2, "mvlt_gemm_nt: out_dtype is 0 (bf16), 1 (fp32) or 2 (fp16, with col_sum only)");
   MVLT_REQUIRE(a->out_dtype != 2 || (a->dtype == 0 && a->col_sum && a->act == 0 && !a->R && !a->row_scale && a->split_k <= 1 && a->c_map.mode == 0 && a->N % 8 == 0 &&
-                                     a->ldc % 8 == 0 && ((uintptr_t)a->C & 15) == 0 && a->M < (1 << 24) && !getenv("MVLT_NT_GENERIC_EPI")),
+                                     a->ldc % 8 == 0 && ((uintptr_t)a->C & 15) == 0 && a->M < (1 << 24)),
                "mvlt_gemm_nt: fp16 output exists in the column-statistics epilogue of the bf16 LDS-DMA kernels only (plain c_map, N % 8 == 0, 16-byte aligned C)");
   if (int e = check_rowmap(a->a_map, "mvlt_gemm_nt a_map")) return e;
   if (int e = check_rowmap(a->c_map, "mvlt_gemm_nt c_map")) return e;
@@ -2906,8 +2904,7 @@ extern "C" int mvlt_gemm_nt(const mvlt_gemm_nt_args* a, void* stream) {
     // (N % 8 != 0 -- the 30522-word MLM logits -- takes the plain lean epilogue too: its last chunk of a row is stored column by column)
     const bool plain_epi = a->act == 0 && !a->R && !a->row_scale && !a->col_sum && !a->H && a->c_map.mode == 0;
     const bool lean_ok = (a->c_map.mode == 0 || (a->c_map.mode == 1 && a->c_map.c_seg % 8 == 0)) && a->split_k <= 1 && (a->N % 8 == 0 || plain_epi) && a->ldc % 8 == 0 && ((uintptr_t)a->C & 15) == 0 &&
-                         (!a->R || ((uintptr_t)a->R & 15) == 0) && (!a->H || ((uintptr_t)a->H & 15) == 0) && a->M < (1 << 24) &&
-                         !getenv("MVLT_NT_GENERIC_EPI");
+                         (!a->R || ((uintptr_t)a->R & 15) == 0) && (!a->H || ((uintptr_t)a->H & 15) == 0) && a->M < (1 << 24);
     if (lean_ok && a->c_map.mode == 1) {
       if (a->act == 0 && !a->col_sum && !a->R && !a->row_scale) epi = 6;
       else if (a->act == 0 && !a->col_sum && a->R) epi = 7;
@@ -2924,15 +2921,13 @@ extern "C" int mvlt_gemm_nt(const mvlt_gemm_nt_args* a, void* stream) {
     // workgroup fits per CU and covers it (98304x1280x320: 240 -> 220 us, 49152x2048x512: 234 -> 201 us).  Long K loses to the
     // doubled barrier count (K = 2048: 103 -> 125 us), other epilogues are neutral; EPI 4 prefers its two-half H prefetch,
     // whose registers allow two workgroups per CU either way (220 / 213 us against 227 / 217 us).
-    const int bkd = (!narrow && a->a_map.mode == 0 && (epi == 3 || (epi == 4 && !getenv("MVLT_NT_EPI4_BK64"))) && a->K <= 512 && !getenv("MVLT_NT_BK64")) ? 32 : 64;
+    const int bkd = (!narrow && a->a_map.mode == 0 && (epi == 3 || epi == 4) && a->K <= 512) ? 32 : 64;
     const int nkd = bkd == 32 ? (a->K + 31) / 32 : nk;
     int ns = nkd < 2 ? nkd : 2;
-    if (const char* e = getenv("MVLT_NT_NS")) { ns = atoi(e); if (ns > nkd) ns = nkd; if (ns < 2) ns = nkd < 2 ? nkd : 2; if (ns > 6) ns = 6; }
     size_t lds2 = (size_t)ns * (BM + bn) * (bkd * 2);
     if (lds2 < stage) lds2 = stage;
-    static const int early_flag = getenv("MVLT_NT_EARLY") ? (atoi(getenv("MVLT_NT_EARLY")) ? 0x100 : 0) : MVLT_NT_EARLY_DEFAULT;
     const int ns_lds = ns;
-    if (nkd >= 2) ns |= early_flag;                // (a single k-step has nothing to refill)
+    if (nkd >= 2) ns |= MVLT_NT_EARLY_DEFAULT;                // (a single k-step has nothing to refill)
     if (a->post_y) {                            // EPI 8: attn.proj + residual + Block.norm2 (whole rows in one tile)
       MVLT_REQUIRE(epi == 2 && a->N == bn && a->a_map.mode == 0 && a->c_map.mode == 0 && a->c_map.rows_per_batch == 0 && a->post_gamma && a->post_beta &&
                    a->post_mean && a->post_rstd && a->post_ld % 8 == 0 && ((uintptr_t)a->post_y & 15) == 0 && ((uintptr_t)a->post_gamma & 15) == 0,
@@ -2963,8 +2958,7 @@ extern "C" int mvlt_gemm_nt(const mvlt_gemm_nt_args* a, void* stream) {
   } while (0)
     // conv3x3 (a_map mode 2) on an LDS-resident, channel-sliced halo: grids of width 16 / 32 / 64, whole 128-pixel tiles inside one
     // image, 64-multiples of gathered channels, lean epilogue, identity or batch-strided output rows
-    static const bool conv_nt_ok = !getenv("MVLT_NO_CONV_NT");
-    if (conv_nt_ok && a->a_map.mode == 2 && (epi == 1 || epi == 2 || epi == 5) && a->split_k <= 1 && a->a_map.c_seg % 64 == 0 && a->c_map.mode == 0 &&
+    if (a->a_map.mode == 2 && (epi == 1 || epi == 2 || epi == 5) && a->split_k <= 1 && a->a_map.c_seg % 64 == 0 && a->c_map.mode == 0 &&
         (a->a_map.w_in == 16 || a->a_map.w_in == 32 || a->a_map.w_in == 64) && (a->a_map.h_in * a->a_map.w_in) % BM == 0 && a->M % BM == 0 &&
         a->M % (a->a_map.h_in * a->a_map.w_in) == 0 && a->a_map.hw_out == a->a_map.h_in * a->a_map.w_in && a->a_map.w_out == a->a_map.w_in &&
         a->K == 9 * a->a_map.c_seg && a->lda >= a->a_map.c_seg && a->ldb >= a->K) {
@@ -2973,20 +2967,19 @@ extern "C" int mvlt_gemm_nt(const mvlt_gemm_nt_args* a, void* stream) {
     }
     // 8-wave kernels with the 8-phase K-loop (gemm_nt_p8_kernel) for the MFMA-bound shapes of the stage 3-4 MLPs: one workgroup per CU, so the
     // tile height is chosen by whole rounds of 256 CUs (rows x rounds = time): 256 x 256, 192 x 256, or 192 x 320 for N % 320 == 0
-    static const int ntp8 = getenv("MVLT_NT_P8") ? atoi(getenv("MVLT_NT_P8")) : 15;      // bit 0: 256 x 256, bit 1: 192 x 256, bit 2: 192 x 320, bit 3: ragged 256 x 256 (EPI 1)
-    if (ntp8 && a->a_map.mode == 0 && a->a_map.rows_per_batch == 0 && a->c_map.mode == 0 && epi >= 1 && epi <= 5 && a->K % 64 == 0 && a->K >= 128) {
+    if (a->a_map.mode == 0 && a->a_map.rows_per_batch == 0 && a->c_map.mode == 0 && epi >= 1 && epi <= 5 && a->K % 64 == 0 && a->K >= 128) {
       auto cost = [&](int bm, int bn) -> long {                         // rows x rounds; 0 = shape does not fit
         if (a->M % bm || a->N % bn) return 0;
         const long tiles = (long)(a->M / bm) * (a->N / bn);
         if (tiles < 192) return 0;
         return ((tiles + 255) / 256) * (long)bm * bn;
       };
-      const long c256 = (ntp8 & 1) ? cost(256, 256) : 0, c192 = (ntp8 & 2) ? cost(192, 256) : 0;
+      const long c256 = cost(256, 256), c192 = cost(192, 256);
       // (192 x 320 with the fp32 residual epilogue pays from K = 640 on: 98304 x 320 x 320 + R 93 us against 73 us on the 128-wide kernel, K = 1280 138 against 155)
-      const long c320 = ((ntp8 & 4) && a->N % 256 != 0 && (epi == 1 || (epi == 2 && (a->K >= 640 || (ntp8 & 16))))) ? cost(192, 320) : 0;
+      const long c320 = (a->N % 256 != 0 && (epi == 1 || (epi == 2 && a->K >= 640))) ? cost(192, 320) : 0;
       bool done = false;
       // ragged M / N (the MLM logits, ~1500 x 30522 x 768, fp32 out): 256 x 256 tiles with the loader clamped at the last row and the checked epilogue
-      if (!c320 && !c256 && !c192 && epi == 1 && (ntp8 & 8) && (a->M % 256 || a->N % 256)) {
+      if (!c320 && !c256 && !c192 && epi == 1 && (a->M % 256 || a->N % 256)) {
         const long tiles = (long)((a->M + 255) / 256) * ((a->N + 255) / 256);
         // ... when the whole rounds of padded tiles are at least 85 % real work: 294912 x 128 would pad half of every 256-wide tile (36 -> 56 us), and
         // 1558 selected rows make 7 x 120 tiles = 4 rounds where 1490 rows make 3 (the 128-wide kernel then wins)
@@ -2996,7 +2989,7 @@ extern "C" int mvlt_gemm_nt(const mvlt_gemm_nt_args* a, void* stream) {
       // ragged M on the 192 x 320 tile (round 6; N % 320 == 0, same epilogue rules as the whole-tile form): pvlt_medium at 384 px runs its 18 stage-3 blocks at
       // M = 45056 = 234.67 x 192 rows -- 235 tiles = ONE round at 92 % -- and took the 128-wide kernels for every N = 320 product (fc2 76 us, fc1 input gradient 66 us,
       // q / proj 27 us: profiles/r06_medium384_gemm_shapes.txt); taken when the whole rounds of padded tiles are >= 85 % real work
-      if (!done && !c320 && !c256 && !c192 && (ntp8 & 4) && a->N % 320 == 0 && a->N % 256 != 0 && a->M % 192 != 0 && (epi == 1 || (epi == 2 && (a->K >= 640 || (ntp8 & 16))))) {
+      if (!done && !c320 && !c256 && !c192 && a->N % 320 == 0 && a->N % 256 != 0 && a->M % 192 != 0 && (epi == 1 || (epi == 2 && a->K >= 640))) {
         const long tiles = (long)((a->M + 191) / 192) * (a->N / 320);
         const long rounds = (tiles + 255) / 256;
         if (tiles >= 192 && (double)a->M * a->N >= 0.85 * (double)rounds * 256.0 * 192.0 * 320.0) {
@@ -3013,7 +3006,7 @@ extern "C" int mvlt_gemm_nt(const mvlt_gemm_nt_args* a, void* stream) {
     }
     // N % 192 == 0 (the 192-channel convolutions): one 192-wide tile instead of 128 + a half-empty 128
     const bool wide = !narrow && a->N % 192 == 0 && a->N % 128 != 0 && (epi == 1 || epi == 5) && a->c_map.mode == 0 && a->a_map.mode != 1 &&
-                      a->K >= 128 && !getenv("MVLT_NT_NO192");
+                      a->K >= 128;
     if (wide) {
       const int tn192 = a->N / 192;
       dim3 grid192((unsigned)(8 * ((tiles_m + 7) / 8) * tn192), 1);
@@ -3077,10 +3070,12 @@ extern "C" int mvlt_gemm_tn(const mvlt_gemm_tn_args* a, void* stream) {
   if (a->M == 0) return MVLT_OK;
   hipStream_t s = (hipStream_t)stream;
   const int mtiles = (a->M + TBK - 1) / TBK;
+  // a split of the LDS-DMA kernel must bring at least 8 k-tiles of work to its N1*N2 atomics: the kv / text-row weight gradients (32768 or 16384
+  // rows, 256 x 128 outputs) ran 256 splits of 1-2 k-tiles, 49 us where 32-64 splits take 20-26 us
+  constexpr int TN_MIN_TILES = 8;
   // conv3x3 weight gradient with an LDS-resident halo (conv3_wgrad_kernel): 3x3 gather on B over a W x H grid with W in {8, 16, 32, 64},
   // whole 64-pixel k-tiles inside one image, 64-multiples of channels, plain [out][tap*cin + c] output
-  static const bool conv_wgrad_ok = !getenv("MVLT_NO_CONV_WGRAD");
-  if (conv_wgrad_ok && a->dtype == 0 && a->b_map.mode == 2 && a->a_map.mode == 0 && a->a_map.rows_per_batch == 0 && !a->trans_c && a->c_taps <= 1 &&
+  if (a->dtype == 0 && a->b_map.mode == 2 && a->a_map.mode == 0 && a->a_map.rows_per_batch == 0 && !a->trans_c && a->c_taps <= 1 &&
       !a->colsum_a && !a->colsum_b && a->N1 % 64 == 0 && a->b_map.c_seg % 64 == 0 && a->N2 == 9 * a->b_map.c_seg && a->M % 64 == 0 &&
       (a->b_map.w_in == 8 || a->b_map.w_in == 16 || a->b_map.w_in == 32 || a->b_map.w_in == 64) && (a->b_map.h_in * a->b_map.w_in) % 64 == 0 &&
       a->M % (a->b_map.h_in * a->b_map.w_in) == 0 && a->ldb >= a->b_map.c_seg) {
@@ -3095,19 +3090,17 @@ extern "C" int mvlt_gemm_tn(const mvlt_gemm_tn_args* a, void* stream) {
   //  atomics that combine the splits complete at ~0.3 floats per ns chip-wide whatever their scope or coalescing: 55 us of tail per launch,
   //  147 us against the 122 us of the 128 x 128 tiles below with their 8 splits and a second workgroup per CU to hide the tail.  DESIGN.md 6.)
   // whole 256 x 256 output tiles, 16 .. 64 of them (= 16 .. 4 m-splits for one workgroup per CU), and a scratch buffer from the caller: the 8-wave / 8-phase TN loop with
-  // bf16 partial tiles + an ordered fold instead of fp32 atomics (gemm_tn_p8_kernel; MVLT_TN_P8=0 keeps the atomic path).  Fewer tiles mean more splits than the fold is
+  // bf16 partial tiles + an ordered fold instead of fp32 atomics (gemm_tn_p8_kernel).  Fewer tiles mean more splits than the fold is
   // worth (8 tiles: 75 us either way), more do not occur in this model.
-  static const bool tnp8 = !(getenv("MVLT_TN_P8") && atoi(getenv("MVLT_TN_P8")) == 0);
-  if (tnp8 && a->partials && a->dtype == 0 && a->a_map.mode == 0 && a->b_map.mode == 0 && a->a_map.rows_per_batch == 0 && a->b_map.rows_per_batch == 0 && a->c_taps <= 1 &&
+  if (a->partials && a->dtype == 0 && a->a_map.mode == 0 && a->b_map.mode == 0 && a->a_map.rows_per_batch == 0 && a->b_map.rows_per_batch == 0 && a->c_taps <= 1 &&
       !a->trans_c && !a->dgrad_out && a->M % 64 == 0 && a->N1 % 256 == 0 && a->N2 % 256 == 0 && a->ldc % 4 == 0 && ((uintptr_t)a->C & 15) == 0 && ((uintptr_t)a->partials & 15) == 0) {
     const int tiles = (a->N1 / 256) * (a->N2 / 256), nkt = a->M / 64;
     if (tiles >= 16 && tiles <= 64 && nkt / (256 / tiles) >= 16 && a->partials_bytes >= (long)(256 / tiles) * a->N1 * a->N2 * 2)
       return launch_tn_p8_partial<4, 2, 2>(*a, s);
   }
   // round 6: one side a multiple of 320, the other >= 1024 (the fc weight gradients of stage 3: 1280 x 320 and 320 x 1280): 192 x 320 tiles of the 8-phase TN loop, 6-16 of
-  // them, the last row tile ragged when it is >= 85 % full overall; bf16 partial tiles + the ordered fold (MVLT_TN_P8_320=0: the 128-wide kernel as in round 5)
-  static const bool tn320 = !(getenv("MVLT_TN_P8_320") && atoi(getenv("MVLT_TN_P8_320")) == 0);
-  if (tnp8 && tn320 && a->partials && a->dtype == 0 && a->a_map.mode == 0 && a->b_map.mode == 0 && a->a_map.rows_per_batch == 0 && a->b_map.rows_per_batch == 0 && a->c_taps <= 1 &&
+  // them, the last row tile ragged when it is >= 85 % full overall; bf16 partial tiles + the ordered fold (round 5 ran them on the 128-wide kernel)
+  if (a->partials && a->dtype == 0 && a->a_map.mode == 0 && a->b_map.mode == 0 && a->a_map.rows_per_batch == 0 && a->b_map.rows_per_batch == 0 && a->c_taps <= 1 &&
       !a->trans_c && !a->dgrad_out && a->M % 64 == 0 && a->N1 % 8 == 0 && a->N2 % 8 == 0 && a->ldc % 4 == 0 && ((uintptr_t)a->C & 15) == 0 && ((uintptr_t)a->partials & 15) == 0 &&
       a->lda % 8 == 0 && a->ldb % 8 == 0 && (((uintptr_t)a->A | (uintptr_t)a->B) & 15) == 0) {
     const bool direct = a->N2 % 320 == 0 && a->N1 >= 1024, swapped = !direct && a->N1 % 320 == 0 && a->N2 >= 1024;
@@ -3132,8 +3125,7 @@ extern "C" int mvlt_gemm_tn(const mvlt_gemm_tn_args* a, void* stream) {
                    (((uintptr_t)a->dgrad_out | (uintptr_t)a->dgrad_wt) & 15) == 0,
                    "mvlt_gemm_tn: dgrad_out needs bf16 operands, plain rows, N1 == N2 == 64 or 128, no transposed / tap output, 16-byte aligned buffers");
       int splits = a->splits > 0 ? a->splits : (a->N1 == 64 ? 256 : 384);       // 1081344 x 64: 128 / 192 / 256 / 384 / 512 splits 136 / 90 / 83 / 91 / 85 us; 294912 x 128: 75 / 63 / 60 / 59 / 68
-      static const int min_tiles = getenv("MVLT_TN_MINT") ? atoi(getenv("MVLT_TN_MINT")) : 8;
-      if (min_tiles > 1 && splits > mtiles / min_tiles) splits = mtiles / min_tiles;
+      if (splits > mtiles / TN_MIN_TILES) splits = mtiles / TN_MIN_TILES;
       if (splits >= 8) splits = (splits + 4) / 8 * 8;
       if (splits > mtiles) splits = mtiles;
       if (splits < 1) splits = 1;
@@ -3142,20 +3134,18 @@ extern "C" int mvlt_gemm_tn(const mvlt_gemm_tn_args* a, void* stream) {
       dim3 grid((unsigned)(splits >= 8 ? 8 * ((splits + 7) / 8) : splits)), block(NTHREADS);
       if (a->N1 == 64) {
         const size_t lds = (size_t)4 * TBK * 128 * 2 + 64 * 64 * 2;
-        static bool once = (hipFuncSetAttribute((const void*)gemm_tn_dma_kernel<64, 64, 3, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess);
-        (void)once;
+        mvlt_max_lds<(gemm_tn_dma_kernel<64, 64, 3, 4, true>)>();
         MVLT_LAUNCH((gemm_tn_dma_kernel<64, 64, 3, 4, true>), grid, block, lds, s, *a, m_per_split, 1, 1, splits, (bf16*)nullptr);
       } else {
         const size_t lds = (size_t)2 * TBK * 256 * 2 + 64 * 128 * 2;
-        static bool once = (hipFuncSetAttribute((const void*)gemm_tn_dma_kernel<128, 128, 3, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess);
-        (void)once;
+        mvlt_max_lds<(gemm_tn_dma_kernel<128, 128, 3, 2, true>)>();
         MVLT_LAUNCH((gemm_tn_dma_kernel<128, 128, 3, 2, true>), grid, block, lds, s, *a, m_per_split, 1, 1, splits, (bf16*)nullptr);
       }
       return mvlt_check_launch("mvlt_gemm_tn");
     }
     MVLT_REQUIRE(!a->c_overwrite || (!a->trans_c && a->c_taps <= 1 && a->N2 % 4 == 0 && a->ldc % 4 == 0 && ((uintptr_t)a->C & 15) == 0),
                  "mvlt_gemm_tn: c_overwrite needs the plain output layout, N2 % 4 == 0, ldc % 4 == 0 and a 16-byte aligned C");
-    const bool small_out = a->N1 <= 128 && a->N2 <= 128 && !getenv("MVLT_TN_NO64");
+    const bool small_out = a->N1 <= 128 && a->N2 <= 128;
     const int bmt = (a->N1 <= 64 || small_out) ? 64 : 128, bn = (a->N2 <= 64 || small_out) ? 64 : 128;
     const int t1 = (a->N1 + bmt - 1) / bmt, t2 = (a->N2 + bn - 1) / bn;
     int splits = a->c_overwrite ? 1 : a->splits;
@@ -3164,10 +3154,7 @@ extern "C" int mvlt_gemm_tn(const mvlt_gemm_tn_args* a, void* stream) {
       splits = ((t1 * t2 == 1 ? 384 : 512) + t1 * t2 - 1) / (t1 * t2);     // a single output tile: 384 (1081344 x 64 x 64: 54.7 -> 48.9 us)
       if (splits >= 8) splits = (splits + 4) / 8 * 8;
       if (splits > 4096) splits = 4096;
-      // ... and a split must bring at least 8 k-tiles of work to its N1*N2 atomics: the kv / text-row weight gradients (32768 or 16384
-      // rows, 256 x 128 outputs) ran 256 splits of 1-2 k-tiles, 49 us where 32-64 splits take 20-26 us
-      static const int min_tiles = getenv("MVLT_TN_MINT") ? atoi(getenv("MVLT_TN_MINT")) : 8;
-      if (min_tiles > 1 && splits > mtiles / min_tiles) splits = mtiles / min_tiles;
+      if (splits > mtiles / TN_MIN_TILES) splits = mtiles / TN_MIN_TILES;
     }
     if (splits > mtiles) splits = mtiles;
     if (splits < 1) splits = 1;
@@ -3179,11 +3166,11 @@ extern "C" int mvlt_gemm_tn(const mvlt_gemm_tn_args* a, void* stream) {
     // several splits meeting on an output of >= 65536 elements (>= 8: the C x C and the fc weight gradients of stages 3-4; 24 while every fold was a launch of its own -- with the
     // batched folds 16 / 8 / 4 / 2 all measure 12.98-13.00 k pairs/s against 12.90 at 24): bf16 partial tiles into the caller's scratch
     // + an ordered fold instead of the atomics (14-21 us of a 53-56 us launch, profiles/r05_tn_small_atomics_ablation.txt).  Fewer splits: the atomics are cheaper than a fold launch.
-    static const int part_min = getenv("MVLT_TN_PART_MIN") ? atoi(getenv("MVLT_TN_PART_MIN")) : 8;
+    constexpr int part_min = 8;
     // ... and from 16384 output elements on (65536 through round 5): the SMALL outputs are where many splits hurt most -- text_embed1's 64 x 768 weight gradient over 32768 rows:
-    // 64 splits x 49152 atomics on the same 1536 cache lines = 56 us where its operands are 9 us of HBM time (tools/ubench_tn_smallk.py; MVLT_TN_PART_MINOUT)
-    static const long part_min_out = getenv("MVLT_TN_PART_MINOUT") ? atol(getenv("MVLT_TN_PART_MINOUT")) : 16384;
-    bf16* const part = (tnp8 && a->partials && !a->c_overwrite && splits >= part_min && !a->trans_c && a->c_taps <= 1 && a->N2 % 8 == 0 && a->ldc % 4 == 0 && ((uintptr_t)a->C & 15) == 0 &&
+    // 64 splits x 49152 atomics on the same 1536 cache lines = 56 us where its operands are 9 us of HBM time (tools/ubench_tn_smallk.py)
+    constexpr long part_min_out = 16384;
+    bf16* const part = (a->partials && !a->c_overwrite && splits >= part_min && !a->trans_c && a->c_taps <= 1 && a->N2 % 8 == 0 && a->ldc % 4 == 0 && ((uintptr_t)a->C & 15) == 0 &&
                         (long)a->N1 * a->N2 >= part_min_out)
                            ? fold_acquire(*a, (long)splits * a->N1 * a->N2 * 2, s) : nullptr;
 #define MVLT_TN_LAUNCH(BMT_, BN_, NS_)                                                                                          \

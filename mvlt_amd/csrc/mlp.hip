@@ -1278,12 +1278,11 @@ template <int C> int launch_wgrad(const mvlt_mlp_args& a, hipStream_t s) {
     const size_t lds_t = lds + ((MVLT_GELU_LUT & 1) ? GELU_LUT_BYTES : 0);
     mvlt_max_lds<(mlp_wgrad2_kernel<C, NW>)>();
     // the token splits' partial tiles of dW1 and dW2 in the caller's scratch (ONE region for both, room for two descriptors) + two folds behind the kernel -- launched at
-    // once, or appended to the scratch's pending table when the caller defers (MVLT_MLP_DW_PARTIALS=0: fp32 atomics as in round 5)
-    static const bool part_ok = !(getenv("MVLT_MLP_DW_PARTIALS") && atoi(getenv("MVLT_MLP_DW_PARTIALS")) == 0);
+    // once, or appended to the scratch's pending table when the caller defers (no scratch: fp32 atomics as in round 5)
     bf16 *part1 = nullptr, *part2 = nullptr;
     mvlt_gemm_tn_args f1 = {}, f2 = {};
     const long pbytes = (long)splits * a.hid * C * 2;
-    if (part_ok && a.partials && ((uintptr_t)a.dw1 & 15) == 0 && ((uintptr_t)a.dw2 & 15) == 0) {
+    if (a.partials && ((uintptr_t)a.dw1 & 15) == 0 && ((uintptr_t)a.dw2 & 15) == 0) {
       f1.C = a.dw1; f1.N1 = a.hid; f1.N2 = C; f1.ldc = C;
       f2.C = a.dw2; f2.N1 = C; f2.N2 = a.hid; f2.ldc = a.hid;
       f1.partials = f2.partials = a.partials; f1.partials_bytes = f2.partials_bytes = a.partials_bytes; f1.defer_fold = f2.defer_fold = a.defer_fold;

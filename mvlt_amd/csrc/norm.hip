@@ -463,7 +463,7 @@ int pick_group(int C) {
 
 template <typename T, typename TY, int G, int ITS, int RU> void launch_fwd_fixed(const mvlt_layernorm_args& a, hipStream_t s) {
   constexpr int GROUPS = NT / G;
-  static const int cap = getenv("MVLT_LN_GRID") ? atoi(getenv("MVLT_LN_GRID")) : 8192;
+  constexpr int cap = 8192;
   long grid = ((long)a.rows + GROUPS * RU - 1) / (GROUPS * RU);
   if (grid > cap) grid = cap;
   MVLT_LAUNCH((ln_fwd_fixed_kernel<T, TY, G, ITS, RU>), dim3((unsigned)grid), dim3(NT), 0, s, a);
@@ -471,19 +471,16 @@ template <typename T, typename TY, int G, int ITS, int RU> void launch_fwd_fixed
 
 template <typename T, typename TY> int launch_fwd(const mvlt_layernorm_args& a_in, hipStream_t s) {
   // the widths of this model get an exact (lanes, chunks) split; everything else takes the power-of-two group kernel
-  static const bool fixed_ok = !getenv("MVLT_LN_GENERIC");
   const bool fixed_c = a_in.C == 64 || a_in.C == 128 || a_in.C == 320 || a_in.C == 512 || a_in.C == 768;
   const mvlt_layernorm_args& a = a_in;
-  MVLT_REQUIRE(!a.y2 || (fixed_ok && fixed_c), "mvlt_layernorm_fwd: the chained second LayerNorm (y2) needs C in {64, 128, 320, 512, 768}, got %d", a.C);
-  if (fixed_ok) {
-    switch (a.C) {
-      case 64: launch_fwd_fixed<T, TY, 8, 1, 2>(a, s); return mvlt_check_launch("mvlt_layernorm_fwd");
-      case 128: launch_fwd_fixed<T, TY, 16, 1, 2>(a, s); return mvlt_check_launch("mvlt_layernorm_fwd");
-      case 320: launch_fwd_fixed<T, TY, 8, 5, 1>(a, s); return mvlt_check_launch("mvlt_layernorm_fwd");
-      case 512: launch_fwd_fixed<T, TY, 16, 4, 1>(a, s); return mvlt_check_launch("mvlt_layernorm_fwd");
-      case 768: launch_fwd_fixed<T, TY, 32, 3, 1>(a, s); return mvlt_check_launch("mvlt_layernorm_fwd");
-      default: break;
-    }
+  MVLT_REQUIRE(!a.y2 || fixed_c, "mvlt_layernorm_fwd: the chained second LayerNorm (y2) needs C in {64, 128, 320, 512, 768}, got %d", a.C);
+  switch (a.C) {
+    case 64: launch_fwd_fixed<T, TY, 8, 1, 2>(a, s); return mvlt_check_launch("mvlt_layernorm_fwd");
+    case 128: launch_fwd_fixed<T, TY, 16, 1, 2>(a, s); return mvlt_check_launch("mvlt_layernorm_fwd");
+    case 320: launch_fwd_fixed<T, TY, 8, 5, 1>(a, s); return mvlt_check_launch("mvlt_layernorm_fwd");
+    case 512: launch_fwd_fixed<T, TY, 16, 4, 1>(a, s); return mvlt_check_launch("mvlt_layernorm_fwd");
+    case 768: launch_fwd_fixed<T, TY, 32, 3, 1>(a, s); return mvlt_check_launch("mvlt_layernorm_fwd");
+    default: break;
   }
   int g = pick_group(a.C);
   MVLT_REQUIRE(g * MAXIT * VN >= a.C, "mvlt_layernorm_fwd: C=%d too large", a.C);
@@ -507,9 +504,9 @@ template <typename T, typename TX, typename TDX> int launch_bwd(const mvlt_layer
   // every workgroup ends with 2*C atomics on the same few cache lines: the rows are spread over few, large workgroups (1024
   // threads, one per CU).  (Storing the partial rows plainly and adding them in a second launch was measured: same time.)  Same time as 1024 x 256 threads
   // on most shapes, 123 -> 96 us at 98304 x 320 (fp32 x, dx +=); more workgroups of either size are slower (1536 x 256: +10 %)
-  // only the two instantiated workgroup sizes: the per-wave LDS slices below are sized from this value (512 used to size 8 slices for a 16-wave launch)
-  static const int nt = (getenv("MVLT_LN_BWD_NT") && atoi(getenv("MVLT_LN_BWD_NT")) == 256) ? 256 : 1024;
-  static const int bcap = getenv("MVLT_LN_BWD_GRID") ? atoi(getenv("MVLT_LN_BWD_GRID")) : 256;
+  // the one instantiated workgroup size: the per-wave LDS slices below are sized from this value (512 used to size 8 slices for a 16-wave launch)
+  constexpr int nt = 1024;
+  constexpr int bcap = 256;
   int groups = nt / g;
   int grid = (a.rows + groups - 1) / groups;
   if (grid > bcap) grid = bcap;
@@ -517,21 +514,16 @@ template <typename T, typename TX, typename TDX> int launch_bwd(const mvlt_layer
   const bool one = g * VN >= a.C;               // one chunk per lane covers the row
   size_t lds = ((size_t)(nt / 64) * 2 + (one ? 0 : 1)) * a.C * sizeof(float);      // per-wave dgamma / dbeta slices (+ gamma): 101 KB at C = 768
   // the dynamic-LDS ceiling is raised ONCE per instantiation (160 KB: whatever C a later call brings) and its result checked
-#define MVLT_LN_BWD_K(KERN_, NT_)                                                                                    \
+#define MVLT_LN_BWD_K(KERN_)                                                                                    \
   do {                                                                                                               \
     static const hipError_t attr = hipFuncSetAttribute((const void*)KERN_, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
     MVLT_REQUIRE(lds <= 65536 || attr == hipSuccess, "mvlt_layernorm_bwd: cannot raise the dynamic LDS limit: %s", hipGetErrorString(attr)); \
-    MVLT_LAUNCH(KERN_, dim3(grid), dim3(NT_), lds, s, a);                                                     \
-  } while (0)
-#define MVLT_LN_BWD_N(G_, NT_)                                                                                       \
-  do {                                                                                                               \
-    if (one) MVLT_LN_BWD_K((ln_bwd_kernel<T, TX, TDX, G_, 1, NT_>), NT_);                                            \
-    else MVLT_LN_BWD_K((ln_bwd_kernel<T, TX, TDX, G_, MAXIT, NT_>), NT_);                                            \
+    MVLT_LAUNCH(KERN_, dim3(grid), dim3(nt), lds, s, a);                                                      \
   } while (0)
 #define MVLT_LN_BWD(G_)                                                                                              \
   do {                                                                                                               \
-    if (nt == 256) MVLT_LN_BWD_N(G_, 256);                                                                           \
-    else MVLT_LN_BWD_N(G_, 1024);                                                                                    \
+    if (one) MVLT_LN_BWD_K((ln_bwd_kernel<T, TX, TDX, G_, 1, nt>));                                                  \
+    else MVLT_LN_BWD_K((ln_bwd_kernel<T, TX, TDX, G_, MAXIT, nt>));                                                  \
   } while (0)
   switch (g) {
     case 8: MVLT_LN_BWD(8); break;
@@ -540,7 +532,6 @@ template <typename T, typename TX, typename TDX> int launch_bwd(const mvlt_layer
     default: MVLT_LN_BWD(64); break;
   }
 #undef MVLT_LN_BWD
-#undef MVLT_LN_BWD_N
 #undef MVLT_LN_BWD_K
   return mvlt_check_launch("mvlt_layernorm_bwd");
 }

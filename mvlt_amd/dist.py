@@ -22,8 +22,6 @@ import torch.nn as nn
 
 # test switch: issue every collective even at world size 1 (a one-GPU box then exercises the RCCL calls of the N > 1 path)
 _FORCE = bool(os.environ.get("MVLT_DP_FORCE_COLLECTIVES"))
-# A/B + test switch: wait for every collective at the end of the backward and step all parameters in one AdamW launch (round 4's behaviour)
-_ONE_LAUNCH = bool(os.environ.get("MVLT_ADAMW_ONE_LAUNCH"))
 
 
 class DataParallel(nn.Module):
@@ -176,7 +174,7 @@ class DataParallel(nn.Module):
         # over un-waited -- FusedAdamW.step steps the ranges whose collectives went out during the backward (pvlt_tiny: 57 of 153 MB) while the tail
         # (the tied word-embedding table, final only with the last kernel of the pass) is still on the wire, then the tail.  Anyone else gets final gradients.
         store.grad_works, self._works = self._works, []
-        if not (store.scale_in_optimizer and not _ONE_LAUNCH):
+        if not store.scale_in_optimizer:
             store.wait_grads()
         store._ranges_done = []
         store.scale_grads(1.0 / self.world)          # DDP's mean; folded into the fused AdamW kernel when that is the optimizer

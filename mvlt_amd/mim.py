@@ -7,8 +7,6 @@ not convert to SyncBN) or the running statistics (eval), in fp32; the align_corn
 feature products are fp32 kernels of csrc/mim.hip.  torch.cat is replaced by writing into column slices of the
 concatenated buffers.  MFMA operands are the only tensors in the compute dtype.
 """
-import os
-
 import torch
 
 from . import ops
@@ -16,16 +14,10 @@ from .params import pool_zeros
 from ._lib import conv3map, rowmap
 
 BN_EPS, BN_MOM = 1e-5, 0.1
-_SEPARATE_STATS = bool(__import__('os').environ.get('MVLT_MIM_SEPARATE_STATS'))   # A/B switch: statistics by a second pass over z
-STAT_COPIES = int(os.environ.get("MVLT_MIM_STAT_COPIES", "16"))           # interleaved batch-statistic accumulators of the conv epilogue (see mvlt_gemm_nt_args.col_copies)
+STAT_COPIES = 16           # interleaved batch-statistic accumulators of the conv epilogue (see mvlt_gemm_nt_args.col_copies)
 CONVS = ("reduction1", "reduction2", "reduction3", "conv_upsample1", "conv_upsample2", "conv_upsample3", "conv_upsample4",
          "conv_upsample5", "conv_concat2", "conv_concat3", "conv4")
-
-
-_FP32_DY = bool(os.environ.get("MVLT_MIM_FP32_DY"))      # A/B switch: every gradient map of the decoder's backward in fp32
-_FP32_Z = bool(os.environ.get("MVLT_MIM_FP32_Z"))        # A/B switch: the pre-BatchNorm conv outputs stay fp32 on the bf16 path (rounds 1-3)
-_NO_FIN_FUSE = bool(os.environ.get("MVLT_MIM_NO_FIN_FUSE"))   # A/B switch: BatchNorm statistics finalised by their own launch
-_NO_BN_FOLD = bool(os.environ.get("MVLT_MIM_NO_BN_FOLD"))   # A/B switch: eval mode keeps the separate BatchNorm pass over an fp32 z
+_NO_BN_FOLD = False      # True (set in-process by the eval tests and tools/ubench_eval.py): eval mode keeps the separate BatchNorm pass over an fp32 z
 
 
 def _z(shape, dev, dtype=torch.float32):
@@ -64,19 +56,15 @@ class MimStep:
             return r
         # z, the conv output BatchNorm normalises: written once, read three times (normalise, the two backward passes) and never an MFMA operand.  On
         # the bf16 path it is kept in fp16 -- the type the reference's autocast gives it -- with the batch statistics taken from the rounded values
-        z16 = self.training and self.dt == torch.bfloat16 and not _FP32_Z and not _SEPARATE_STATS
+        z16 = self.training and self.dt == torch.bfloat16
         z = _e((M, cout), dev, torch.float16 if z16 else torch.float32)
         st = _z((2, STAT_COPIES, cout), dev) if self.training else (None, None)   # batch statistics ride on the conv's epilogue
-        if _SEPARATE_STATS and self.training:
-            ops.gemm_nt(xin, S.extra[p + ".0.weight::K"], z, M, cout, 9 * cin, ld_in, 9 * cin, cout, a_map=amap)
-            ops.col_stats(z, cout, M, cout, st[0][0], st[1][0])
-        else:
-            ops.gemm_nt(xin, S.extra[p + ".0.weight::K"], z, M, cout, 9 * cin, ld_in, 9 * cin, cout, a_map=amap, col_sum=st[0], col_sumsq=st[1],
-                        col_copies=STAT_COPIES)
+        ops.gemm_nt(xin, S.extra[p + ".0.weight::K"], z, M, cout, 9 * cin, ld_in, 9 * cin, cout, a_map=amap, col_sum=st[0], col_sumsq=st[1],
+                    col_copies=STAT_COPIES)
         fin = None
         if self.training:
             mean, rstd = _e((cout,), dev), _e((cout,), dev)
-            if z16 and cout % 8 == 0 and cout <= 256 and not _NO_FIN_FUSE:
+            if z16 and cout % 8 == 0 and cout <= 256:
                 # the statistics are finalised in the prologue of the normalisation launch (`norm`): eleven tiny launches fewer per step
                 fin = (st[0], st[1], bn.running_mean, bn.running_var)
             else:
@@ -140,7 +128,7 @@ class MimStep:
         # reductions of the three pyramid levels to 64 channels
         # the three factors of the full-resolution feature product (low, cu2o, cu3o: written once, read by the product and by its backward, never an
         # MFMA operand) are fp16 beside the fp16 z on the bf16 training path: 0.3 GB less traffic per step
-        f16 = torch.float16 if (self.training and dt == torch.bfloat16 and not _FP32_Z and not _SEPARATE_STATS and not _FP32_DY) else torch.float32
+        f16 = torch.float16 if (self.training and dt == torch.bfloat16) else torch.float32
         r = self.conv_bn("reduction1", x2, C2, x2.shape[1], s1, C2, ch, M1); low = _e((M1, ch), dev, f16); self.norm(r, low, ch)
         r = self.conv_bn("reduction2", x3, C3, x3.shape[1], s2, C3, ch, M2); mid = _e((M2, ch), dev); self.norm(r, mid, ch)
         r = self.conv_bn("reduction3", x4, C4, x4.shape[1], s3, C4, ch, M3); high = _e((M3, ch), dev); self.norm(r, high, ch)
@@ -229,7 +217,7 @@ class MimStep:
                     colsum=S.grad("t2i_head.score.0.bias"))
         # the three 192-channel gradient maps at full resolution travel in the operand dtype (each is written once and read twice by the
         # BatchNorm backward behind it: 0.9 GB less traffic per step at batch 256); the maps further down stay fp32 (they are accumulated into)
-        gd = dt if (dt == torch.bfloat16 and not _FP32_DY) else torch.float32
+        gd = dt if dt == torch.bfloat16 else torch.float32
         de = _e((M1, 3 * ch), dev, gd)
         ops.gemm_nt(dsc_p, S.extra["t2i_head.score.0.weight::T"], de, M1, 3 * ch, 8, 8, 8, 3 * ch)
         dd = self.bn_conv_bwd("conv4", de, 3 * ch, dx_dtype=gd)

@@ -7,8 +7,6 @@ get weight_decay 0, everything else args.weight_decay.  It is a torch.optim.Opti
 lr schedulers (`param_groups[i]['lr']`) and state_dict()/load_state_dict() keep working; `param_groups[0]` is the
 no-decay group and `[1]` the decay group, like timm's add_weight_decay.
 """
-import os
-
 import torch
 
 from . import ops
@@ -87,7 +85,7 @@ class FusedAdamW(torch.optim.Optimizer):
             # the step's scalars reach the device through a ring of PINNED rows: from a pageable source hipMemcpyAsync stages the copy on
             # the host and the call returns only when the stream has drained -- the host then enqueues the optimizer kernel and the whole
             # next forward behind an idle GPU (1.3 ms per fine-tune step, tools/host_time.py).  An event per row guards its reuse.
-            self._hp_pin = torch.zeros(4, 8).pin_memory() if S.P.is_cuda and not os.environ.get("MVLT_HP_PAGEABLE") else None
+            self._hp_pin = torch.zeros(4, 8).pin_memory() if S.P.is_cuda else None
             self._hp_ev = [None] * 4
             # one byte per parameter: 1 = weight decay applies (timm's split: not for 1-D tensors / biases)
             ids_nd = {id(p) for p in self.param_groups[0]["params"]}

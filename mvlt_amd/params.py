@@ -11,7 +11,6 @@ Memory layout (sized for 288 GB HBM: everything stays resident)
       copy W^T (dgrad operand) and conv weights a [out][kh][kw][cin] re-ordering (patch-GEMM operand)
 """
 import math
-import os
 import weakref
 from collections import OrderedDict
 
@@ -20,9 +19,7 @@ import torch.nn as nn
 
 from . import ops
 
-_EARLY_FOLDS = bool(os.environ.get("MVLT_EARLY_FOLDS"))        # A/B switch: gradient-copy folds after every backward stage also without a data-parallel wrapper
-_TN_SCRATCH_MIB = int(os.environ.get("MVLT_TN_SCRATCH_MIB", "256"))      # scratch of the weight-gradient partial tiles (deferred folds keep several launches' tiles in it)
-_PREP_FP32_SRC = bool(os.environ.get("MVLT_PREP_FP32_SRC"))     # A/B switch: transposed weight copies read the fp32 masters (rounds 1-3)
+_TN_SCRATCH_MIB = 256      # scratch of the weight-gradient partial tiles (deferred folds keep several launches' tiles in it)
 ALIGN = 8
 
 
@@ -278,7 +275,7 @@ class FlatStore:
             k = name + "::T"
             if k not in self.extra or self.extra[k].dtype != dt or self.extra[k].device != dev:
                 self.extra[k] = torch.zeros(Ccols, ld, device=dev, dtype=dt)
-            if self.C is not None and dt == torch.bfloat16 and Ccols % 8 == 0 and not _PREP_FP32_SRC:
+            if self.C is not None and dt == torch.bfloat16 and Ccols % 8 == 0:
                 # W^T from the bf16 copy of the parameters (fresh whenever this launch runs: refresh() casts first, or the fused optimizer step wrote
                 # it): identical values -- bf16(W)^T -- at half the bytes read, in 16-byte accesses
                 descs.append(PrepDesc(self.comp(name).data_ptr(), self.extra[k].data_ptr(), 2, R, Ccols, ld, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
@@ -423,7 +420,7 @@ class FlatStore:
     # atomics at all -- and one `mvlt_fold_copies` launch per backward stage sums the copies into G (and zeroes the ones that were written).
     # Arena slots are handed out in first-use order, so a stage's slots are one contiguous range; a copy has room for every 1-D parameter of the
     # model, whatever its depth (pvlt_tiny: 256 x 56 k floats = 57 MB).
-    LN_COPIES = int(os.environ.get("MVLT_LN_COPIES", "256"))
+    LN_COPIES = 256
 
     @property
     def ln_stride(self):
@@ -459,7 +456,7 @@ class FlatStore:
         each trunk stage): without a wrapper they wait for the fold at the end of the trunk's backward -- two launches per step instead of nine
         (every small launch between two large ones costs several times its own duration in drained pipelines)."""
         from . import ops
-        if early and self.on_range_ready is None and not _EARLY_FOLDS:
+        if early and self.on_range_ready is None:
             return
         if self.G.is_cuda:
             self.tn_fold_flush()             # deferred partial-tile folds of the weight-gradient GEMMs (their conv outputs land in the tap arena folded next)

@@ -8,8 +8,6 @@ Data layout: one token-major activation buffer (B, HW+T, C) per stage in the com
 Backward is scheduled by hand: every weight gradient is accumulated by the wgrad GEMM directly into the flat fp32
 gradient buffer (no autograd accumulate pass), input gradients reuse buffers in place.
 """
-import os
-
 import torch
 import torch.nn.functional as F
 
@@ -23,41 +21,10 @@ def _empty(shape, dtype, dev):
     return torch.empty(shape, dtype=dtype, device=dev)
 
 
-_LN_COPIES = not os.environ.get("MVLT_LN_NO_COPIES")      # A/B switch: LayerNorm parameter gradients by plain atomics
-_NO_DX2 = bool(os.environ.get("MVLT_NO_DX2"))      # A/B switch: DropPath-scaled gradient copy by a separate pass
-_NO_T2I_FUSE = bool(os.environ.get("MVLT_NO_T2I_FUSE"))    # A/B switch: t2i_logits materialised, SmoothL1 as its own two passes
-_NO_LN_CHAIN = bool(os.environ.get("MVLT_NO_LN_CHAIN")) or bool(os.environ.get("MVLT_LN_GENERIC"))   # A/B switch: first block's norm1 as its own launch
-_NO_LNB_FUSE = bool(os.environ.get("MVLT_NO_LNB_FUSE"))    # A/B switch: norm2's backward as its own launch behind the fused-MLP dx kernel
-_NO_POST_LN = bool(os.environ.get("MVLT_NO_POST_LN"))      # A/B switch: every block launches its own norm1
-_NO_OUT_OP = bool(os.environ.get("MVLT_NO_OUT_OP"))        # A/B switch: fp32 stage output + separate cast pass
-_NO_PROJ_LN = bool(os.environ.get("MVLT_NO_PROJ_LN"))      # A/B switch: LN2 folded into the fused MLP's operand load (round 2) instead of the proj epilogue
-_NO_LN_FOLD = bool(os.environ.get("MVLT_NO_LN_FOLD"))      # A/B switch: LN2 as its own launch in front of the fused MLP
-_NO_POS_BATCH = bool(os.environ.get("MVLT_NO_POS_BATCH"))  # A/B switch: one resize launch per stage and direction for the position embeddings
-_NT_GENERIC_EPI = bool(os.environ.get("MVLT_NT_GENERIC_EPI"))   # the library's switch (generic GEMM epilogue): the r_fp32 stage output does not exist there
-_NO_LIN_FUSE = bool(os.environ.get("MVLT_NO_LIN_FUSE"))    # A/B switch: weight and input gradient of the C x C Linears of stages 1-2 as two launches
-# A/B switches: conv weight gradients accumulated straight into the [out][cin][kh][kw] layout by the wgrad epilogue (strided atomics),
-# or through a pooled [out][kh][kw][cin] buffer + one permuted ATen add per convolution, instead of the store's tap arena
-WGRAD_TAPS = bool(os.environ.get("MVLT_WGRAD_TAPS"))
-WGRAD_ADD = bool(os.environ.get("MVLT_WGRAD_ADD"))
-
-
-_NO_OVERWRITE = bool(os.environ.get("MVLT_TN_NO_OVERWRITE"))     # 1: the vocabulary decoder's weight gradient back on fp32 atomics (round 5)
-_DEFER_FOLD = os.environ.get("MVLT_TN_DEFER_FOLD", "1") != "0"     # the weight-gradient folds batched into a few launches (FlatStore.fold_copies flushes); 0 = one fold per GEMM
-
-
 def conv_wgrad(S, name, dz, xin, M, cout, K, ld_dz, ld_in, bmap, taps, cin, colsum=None):
     """weight gradient of a gathered-row convolution into the G slice of nn.Conv2d's (out, cin, kh, kw) weight `name`: accumulated in
     the gather's (out, kh, kw, cin) order in the store's tap arena, which S.fold_copies() adds to G at the (out, cin, kh, kw) places"""
-    if WGRAD_TAPS:
-        ops.gemm_tn(dz, xin, S.grad(name).view(cout, K), M, cout, K, ld_dz, ld_in, K, b_map=bmap, colsum=colsum, taps=taps, seg=cin)
-        return
-    if WGRAD_ADD:
-        dWk = pool_zeros((cout, K), torch.float32, dz.device)
-        ops.gemm_tn(dz, xin, dWk, M, cout, K, ld_dz, ld_in, K, b_map=bmap, colsum=colsum)
-        kk = int(round(taps ** 0.5))
-        S.grad(name).add_(dWk.view(cout, kk, kk, cin).permute(0, 3, 1, 2))
-        return
-    ops.gemm_tn(dz, xin, S.grad_taps(name, cout, taps, cin), M, cout, K, ld_dz, ld_in, K, b_map=bmap, colsum=colsum, partials=S.tn_partials(), defer_fold=_DEFER_FOLD)
+    ops.gemm_tn(dz, xin, S.grad_taps(name, cout, taps, cin), M, cout, K, ld_dz, ld_in, K, b_map=bmap, colsum=colsum, partials=S.tn_partials(), defer_fold=True)
 
 
 def _step_rng(model):
@@ -144,10 +111,14 @@ class TrunkStep:
 
     def gl(self, name):
         """LayerNorm weight / bias gradient: slot of the interleaved accumulators (FlatStore.grad_copies)"""
-        return self.S.grad_copies(name) if _LN_COPIES else self.S.grad(name)
+        return self.S.grad_copies(name)
 
     def lnk(self):
-        return self.S.ln_kwargs() if _LN_COPIES else {}
+        return self.S.ln_kwargs()
+
+    def tn(self):
+        """how the split weight-gradient GEMMs reduce: bf16 partial tiles in the store's scratch, folded in a few batched launches (FlatStore.fold_copies flushes)"""
+        return dict(partials=self.S.tn_partials(), defer_fold=True)
 
     # ---- pos embed: learned for the constructor grid, bilinearly resized (align_corners=False) to this input's grid
     def _pos(self, i, param):
@@ -164,12 +135,7 @@ class TrunkStep:
                                    f"(reference libs/pvlt.py:292 compares every stage with stage 1's {m.grids[0] ** 2} patches): the reference "
                                    f"model cannot run this input size either")
             return pe          # (a non-square stage-1 grid of that count -- 392 x 8 at the default 224 -- adds the square embedding row for row, like the reference)
-        pre = getattr(self, "_pos_pre", None)
-        if pre is not None and i in pre:
-            return pre[i]                      # resized by the one launch at the start of the forward pass (`_pos_prefetch`)
-        out = _empty((HW, C), torch.float32, self.dev)
-        ops.resize_bilinear_tokens(pe, out, m.grids[i], m.grids[i], h, w, C)
-        return out
+        return self._pos_pre[i]                # resized by the one launch at the start of the forward pass (`_pos_prefetch`)
 
     def _pos_prefetch(self):
         """the resized position embeddings of all four stages in ONE launch (they depend on parameters only)"""
@@ -184,10 +150,8 @@ class TrunkStep:
             out = _empty((h * w, C), torch.float32, self.dev)
             jobs.append((pe, out, m.grids[i], m.grids[i], h, w, C))
             self._pos_pre[i] = out
-        if jobs and not _NO_POS_BATCH:
+        if jobs:
             ops.resize_bilinear_tokens_multi(jobs)
-        else:
-            self._pos_pre = None
 
     def _droppath_scales(self, blk_index):
         m = self.m
@@ -265,7 +229,7 @@ class TrunkStep:
         # the first block's norm1 is chained onto the two embedding LayerNorms below (their output rows are in registers): that block
         # launches no LayerNorm of its own and the fp32 rows are not read back
         chain = None
-        if dt == torch.bfloat16 and C in ops.LN_CHAIN_WIDTHS and not _NO_LN_CHAIN:
+        if dt == torch.bfloat16 and C in ops.LN_CHAIN_WIDTHS:
             p0 = Names.blk(i, 0)
             self._pre_ln1 = (_empty((B, N, C), dt, dev), _empty((B * N,), torch.float32, dev), _empty((B * N,), torch.float32, dev))
             chain = (self.f32(p0 + "norm1.weight"), self.f32(p0 + "norm1.bias"), EPS_BLOCK, *self._pre_ln1)
@@ -365,7 +329,7 @@ class TrunkStep:
         bs["fused_mlp"] = fused = (dt == torch.bfloat16 and C in (64, 128))
         # stages 1-2 (one tile of the projection holds whole rows): Block.norm2 rides on the projection's epilogue -- the fused MLP then reads
         # its operand in bf16 and the fp32 mid stream only once (as the residual), instead of normalising the fp32 rows itself
-        proj_ln = fused and not _NO_PROJ_LN and not _NO_LN_FOLD and M < (1 << 24)      # (the lean GEMM epilogues index rows in 24 bits)
+        proj_ln = fused and M < (1 << 24)      # (the lean GEMM epilogues index rows in 24 bits)
         ops.gemm_nt(ao, self.w(p + "attn.proj.weight"), xm, M, C, C, C, C, C, bias=self.f32(p + "attn.proj.bias"),
                     row_scale=s1, rows_per_scale=N, R=x,
                     post_ln=(self.f32(p + "norm2.weight"), self.f32(p + "norm2.bias"), EPS_BLOCK, xn2.view(M, C), bs["m2"], bs["r2"]) if proj_ln else None)
@@ -373,21 +337,19 @@ class TrunkStep:
         # LN2 + MLP (fc1 + exact GELU, fc2) + DropPath + residual
         # the last block of a stage has no fp32 consumer (its output feeds the next stage's patch embedding and the heads, which read
         # the MFMA-operand copy): the fused MLP then writes that copy itself and no fp32 stream -- no separate cast pass
-        last_op = fused and j == m.depths[i] - 1 and self.dt != self.rt and not _NO_OUT_OP
+        last_op = fused and j == m.depths[i] - 1 and self.dt != self.rt
         # stages 3-4: the same through fc2's residual epilogue (bf16 C beside the fp32 residual, mvlt_gemm_nt_args.r_fp32)
         # (r_fp32 exists in the lean residual epilogue only: rows indexed in 24 bits, 16-byte row pieces -- otherwise the fp32 output + cast pass below)
-        last_gemm = ((not fused) and j == m.depths[i] - 1 and dt == torch.bfloat16 and self.rt == torch.float32 and not _NO_OUT_OP and
-                     M < (1 << 24) and C % 8 == 0 and not _NT_GENERIC_EPI)
+        last_gemm = ((not fused) and j == m.depths[i] - 1 and dt == torch.bfloat16 and self.rt == torch.float32 and
+                     M < (1 << 24) and C % 8 == 0)
         xo = _empty((B, N, C), dt if (last_op or last_gemm) else self.rt, dev)
         if fused:
             # stages 1-2: LN2 -> fc1 -> GELU -> fc2 -> DropPath -> +residual in ONE kernel.  The (tokens x hidden) activation stays on
             # chip and is recomputed by the fused backward kernels; LN2 is folded into the operand load (the kernel reads the fp32
             # mid stream once for both the normalisation and the residual, and stores LN2's output + statistics for the backward)
-            ln = None if (_NO_LN_FOLD or proj_ln) else (self.f32(p + "norm2.weight"), self.f32(p + "norm2.bias"), EPS_BLOCK, xn2, bs["m2"], bs["r2"])
-            if ln is None and not proj_ln:
-                ops.layernorm_fwd(xm, xn2, self.f32(p + "norm2.weight"), self.f32(p + "norm2.bias"), M, C, C, C, EPS_BLOCK, mean=bs["m2"], rstd=bs["r2"])
+            ln = None if proj_ln else (self.f32(p + "norm2.weight"), self.f32(p + "norm2.bias"), EPS_BLOCK, xn2, bs["m2"], bs["r2"])
             post = None
-            if j + 1 < m.depths[i] and not _NO_POST_LN:
+            if j + 1 < m.depths[i]:
                 # the next block's norm1 rides on this kernel's epilogue (the output row is in registers there)
                 pn = Names.blk(i, j + 1)
                 self._pre_ln1 = (_empty((B, N, C), dt, dev), _empty((M,), f32, dev), _empty((M,), f32, dev))
@@ -474,7 +436,7 @@ class TrunkStep:
             ops.gemm_tn(d_pe, sv["P1"], self.g(pe + "proj.weight").view(C, K), B * HW, C, K, C, K, K, colsum=self.g(pe + "proj.bias"))
             # (round 6: the text-embedding weight gradients leave as partial tiles too -- 64 x 768 over 32768 rows: 64 splits' atomics on 1536 cache lines were 56 us)
             ops.gemm_tn(d_te, self.emb, self.g(ten + "0.weight"), B * T, C, m.hidden, C, m.hidden, m.hidden, colsum=self.g(ten + "0.bias"),
-                        partials=self.S.tn_partials(), defer_fold=_DEFER_FOLD)
+                        **self.tn())
             d_emb = _empty((B * T, m.hidden), dt, dev)
             ops.gemm_nt(d_te, self.wT(ten + "0.weight"), d_emb, B * T, m.hidden, C, C, C, m.hidden)
             self._bert_backward(d_emb)
@@ -485,7 +447,7 @@ class TrunkStep:
         # conv weight gradient: computed in the gather's [out][kh][kw][cin] order, accumulated at its [out][cin][kh][kw] place
         conv_wgrad(self.S, pe + "proj.weight", d_pe, xp, B * HW, C, 4 * Cp, C, Cp, pm, 4, Cp, colsum=self.g(pe + "proj.bias"))
         ops.gemm_tn(d_te, xp, self.g(ten + "0.weight"), B * T, C, Cp, C, Cp, Cp, b_map=rowmap(T, Np, HWp), colsum=self.g(ten + "0.bias"),
-                    partials=self.S.tn_partials(), defer_fold=_DEFER_FOLD)
+                    **self.tn())
         dxp = into.view(B, Np, Cp) if into is not None else _empty((B, Np, Cp), dt, dev)
         ops.gemm_nt(d_pe, self.wKT(pe + "proj.weight"), dxp, B * HW, 4 * Cp, C, C, C, Cp, c_map=pm, R=into)          # image rows (each once)
         ops.gemm_nt(d_te, self.wT(ten + "0.weight"), dxp, B * T, Cp, C, C, C, Cp, c_map=rowmap(T, Np, HWp), R=into)   # text rows
@@ -500,11 +462,8 @@ class TrunkStep:
         if HW == m.grids[0] ** 2:
             gv.add_(dpos)
             return
-        if _NO_POS_BATCH:
-            ops.resize_bilinear_tokens(dpos, gv, m.grids[i], m.grids[i], h, w, dpos.shape[1], adjoint=True)   # accumulates into G
-        else:
-            # the adjoints of all stages leave in one launch at the end of the trunk's backward (`backward`): dpos stays alive in the list until then
-            self._pos_adj.append((dpos, gv, m.grids[i], m.grids[i], h, w, dpos.shape[1]))
+        # the adjoints of all stages leave in one launch at the end of the trunk's backward (`backward`): dpos stays alive in the list until then
+        self._pos_adj.append((dpos, gv, m.grids[i], m.grids[i], h, w, dpos.shape[1]))
 
     def _bert_backward(self, d_emb):
         m, B, T = self.m, self.B, self.T
@@ -526,57 +485,47 @@ class TrunkStep:
         f32 = torch.float32
         # ---- MLP branch: x_out = x_mid + s2 * (fc2(gelu(fc1(LN2(x_mid)))))
         dxn2 = _empty((M, C), dt, dev)
-        ln2_done = False
+        # the DropPath-scaled copy of d(x_mid), the gradient of the attention branch x_mid = x + s1 * proj(attn(LN1(x))), comes out of norm2's backward
+        fuse = bs["s1"] is not None
         if bs["fused_mlp"]:
             w1, w2t = self.w(p + "mlp.fc1.weight"), self.wT(p + "mlp.fc2.weight")
             ops.mlp_bwd_dw(bs["xn2"], dx, w1, w2t, self.f32(p + "mlp.fc1.bias"), self.g(p + "mlp.fc1.weight"), self.g(p + "mlp.fc1.bias"),
                            self.g(p + "mlp.fc2.weight"), self.g(p + "mlp.fc2.bias"), M, C, hid, row_scale=bs["s2"], rows_per_scale=N,
-                           partials=self.S.tn_partials(), defer_fold=_DEFER_FOLD)
-            if not _NO_LNB_FUSE:
-                # ... and norm2's backward rides on the dx kernel's epilogue (the row of d(LN output) is in registers there): dx is
-                # updated in place, the DropPath-scaled copy for the attention branch comes out of the same pass, no dxn2 round trip
-                fuse = bs["s1"] is not None and not _NO_DX2
-                dy1 = _empty((M, C), dx.dtype, dev) if fuse else dx
-                ops.mlp_bwd_dx(bs["xn2"], dx, w1, self.wT(p + "mlp.fc1.weight"), w2t, self.f32(p + "mlp.fc1.bias"), None, M, C, hid,
-                               row_scale=bs["s2"], rows_per_scale=N,
-                               ln_bwd=dict(x=bs["xm"], mean=bs["m2"], rstd=bs["r2"], gamma=self.f32(p + "norm2.weight"), dx=dx,
-                                           dgamma=self.gl(p + "norm2.weight"), dbeta=self.gl(p + "norm2.bias"),
-                                           dx2=dy1 if fuse else None, dx2_scale=bs["s1"], dx2_rows_per_scale=N))
-                ln2_done = True
-            else:
-                ops.mlp_bwd_dx(bs["xn2"], dx, w1, self.wT(p + "mlp.fc1.weight"), w2t, self.f32(p + "mlp.fc1.bias"), dxn2, M, C, hid,
-                               row_scale=bs["s2"], rows_per_scale=N)
+                           **self.tn())
+            # ... and norm2's backward rides on the dx kernel's epilogue (the row of d(LN output) is in registers there): dx is
+            # updated in place, the DropPath-scaled copy for the attention branch comes out of the same pass, no dxn2 round trip
+            dy1 = _empty((M, C), dx.dtype, dev) if fuse else dx
+            ops.mlp_bwd_dx(bs["xn2"], dx, w1, self.wT(p + "mlp.fc1.weight"), w2t, self.f32(p + "mlp.fc1.bias"), None, M, C, hid,
+                           row_scale=bs["s2"], rows_per_scale=N,
+                           ln_bwd=dict(x=bs["xm"], mean=bs["m2"], rstd=bs["r2"], gamma=self.f32(p + "norm2.weight"), dx=dx,
+                                       dgamma=self.gl(p + "norm2.weight"), dbeta=self.gl(p + "norm2.bias"),
+                                       dx2=dy1 if fuse else None, dx2_scale=bs["s1"], dx2_rows_per_scale=N))
         else:
             dy2 = getattr(self, "_dy2_pre", None)                # written by the block above's norm1 backward when there is one
             self._dy2_pre = None
             if dy2 is None:
                 dy2 = self._scaled(dx, bs["s2"], N)
-            ops.gemm_tn(dy2, bs["gact"], self.g(p + "mlp.fc2.weight"), M, C, hid, C, hid, hid, colsum=self.g(p + "mlp.fc2.bias"), partials=self.S.tn_partials(), defer_fold=_DEFER_FOLD)
+            ops.gemm_tn(dy2, bs["gact"], self.g(p + "mlp.fc2.weight"), M, C, hid, C, hid, hid, colsum=self.g(p + "mlp.fc2.bias"), **self.tn())
             dh = _empty((M, hid), dt, dev)
             ops.gemm_nt(dy2, self.wT(p + "mlp.fc2.weight"), dh, M, hid, C, C, C, hid, act=2, H=bs["hpre"])
             bs["gact"] = bs["hpre"] = None
-            ops.gemm_tn(dh, bs["xn2"], self.g(p + "mlp.fc1.weight"), M, hid, C, hid, C, C, colsum=self.g(p + "mlp.fc1.bias"), partials=self.S.tn_partials(), defer_fold=_DEFER_FOLD)
+            ops.gemm_tn(dh, bs["xn2"], self.g(p + "mlp.fc1.weight"), M, hid, C, hid, C, C, colsum=self.g(p + "mlp.fc1.bias"), **self.tn())
             ops.gemm_nt(dh, self.wT(p + "mlp.fc1.weight"), dxn2, M, C, hid, hid, hid, C)
             del dh
-        # dx += LN2 backward = d(x_mid); the same kernel writes its DropPath-scaled copy, the gradient of the attention branch
-        # x_mid = x + s1 * proj(attn(LN1(x)))
-        if not ln2_done:
-            fuse = bs["s1"] is not None and not _NO_DX2
+            # dx += LN2 backward = d(x_mid); the same kernel writes its DropPath-scaled copy
             dy1 = _empty((M, C), dx.dtype, dev) if fuse else dx
             ops.layernorm_bwd(dxn2, bs["xm"], dx, self.f32(p + "norm2.weight"), bs["m2"], bs["r2"], M, C, C, C, C,
                               dgamma=self.gl(p + "norm2.weight"), dbeta=self.gl(p + "norm2.bias"), **self.lnk(), accumulate=True,
                               dx2=dy1 if fuse else None, dx2_scale=bs["s1"], dx2_rows_per_scale=N, lddx2=C)
-        if not fuse:
-            dy1 = self._scaled(dx, bs["s1"], N)
         # stages 1-2 (C = 64 / 128, HBM-bound): the weight gradient and the input gradient of a C x C Linear come out of ONE pass over dY
-        lin_fuse = dt == torch.bfloat16 and C in (64, 128) and not _NO_LIN_FUSE
+        lin_fuse = dt == torch.bfloat16 and C in (64, 128)
         dao = dxn2          # reuse
         if lin_fuse:
             ops.gemm_tn(dy1, bs["ao"], self.g(p + "attn.proj.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.proj.bias"),
                         dgrad=(self.wT(p + "attn.proj.weight"), dao.view(M, C)))
         else:
             # (stages 3-4: 9-16 output tiles x 32-56 m-splits -- reduced through bf16 partial tiles + a fold instead of atomics: mvlt_gemm_tn_args.partials)
-            ops.gemm_tn(dy1, bs["ao"], self.g(p + "attn.proj.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.proj.bias"), partials=self.S.tn_partials(), defer_fold=_DEFER_FOLD)
+            ops.gemm_tn(dy1, bs["ao"], self.g(p + "attn.proj.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.proj.bias"), **self.tn())
             ops.gemm_nt(dy1, self.wT(p + "attn.proj.weight"), dao, M, C, C, C, C, C)
         Mk = bs["Mk"]
         dq = _empty((B, N, C), dt, dev)
@@ -596,17 +545,17 @@ class TrunkStep:
             ops.gemm_tn(dq, bs["xn1"], self.g(p + "attn.q.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.q.bias"),
                         dgrad=(self.wT(p + "attn.q.weight"), dxn1.view(M, C)))
         else:
-            ops.gemm_tn(dq, bs["xn1"], self.g(p + "attn.q.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.q.bias"), partials=self.S.tn_partials(), defer_fold=_DEFER_FOLD)
+            ops.gemm_tn(dq, bs["xn1"], self.g(p + "attn.q.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.q.bias"), **self.tn())
             ops.gemm_nt(dq, self.wT(p + "attn.q.weight"), dxn1, M, C, C, C, C, C)
         gkvw, gkvb = self.g(p + "attn.kv.weight"), self.g(p + "attn.kv.bias")
         wkvT = self.wT(p + "attn.kv.weight")
         if r > 1:
             HWr, pm = bs["HWr"], bs["pm"]
             # text keys come straight from LN1(x)[text rows]
-            ops.gemm_tn(dkv, bs["xn1"], gkvw, B * T, 2 * C, C, 2 * C, C, C, a_map=rowmap(T, Mk, HWr), b_map=rowmap(T, N, HW), colsum=gkvb, partials=self.S.tn_partials(), defer_fold=_DEFER_FOLD)
+            ops.gemm_tn(dkv, bs["xn1"], gkvw, B * T, 2 * C, C, 2 * C, C, C, a_map=rowmap(T, Mk, HWr), b_map=rowmap(T, N, HW), colsum=gkvb, **self.tn())
             ops.gemm_nt(dkv, wkvT, dxn1, B * T, C, 2 * C, 2 * C, 2 * C, C, a_map=rowmap(T, Mk, HWr), c_map=rowmap(T, N, HW), R=dxn1)
             # image keys: kv <- LN(sr conv(LN1(x)[image rows]))
-            ops.gemm_tn(dkv, bs["kvin"], gkvw, B * HWr, 2 * C, C, 2 * C, C, C, a_map=rowmap(HWr, Mk, 0), colsum=gkvb, partials=self.S.tn_partials(), defer_fold=_DEFER_FOLD)
+            ops.gemm_tn(dkv, bs["kvin"], gkvw, B * HWr, 2 * C, C, 2 * C, C, C, a_map=rowmap(HWr, Mk, 0), colsum=gkvb, **self.tn())
             dkvin = _empty((B * HWr, C), dt, dev)
             ops.gemm_nt(dkv, wkvT, dkvin, B * HWr, C, 2 * C, 2 * C, 2 * C, C, a_map=rowmap(HWr, Mk, 0))
             dsr = _empty((B * HWr, C), dt, dev)
@@ -616,12 +565,12 @@ class TrunkStep:
             conv_wgrad(self.S, p + "attn.sr.weight", dsr, bs["xn1"], B * HWr, C, K, C, C, pm, r * r, C, colsum=self.g(p + "attn.sr.bias"))
             ops.gemm_nt(dsr, self.wKT(p + "attn.sr.weight"), dxn1, B * HWr, K, C, C, C, C, c_map=pm, R=dxn1)
         else:
-            ops.gemm_tn(dkv, bs["xn1"], gkvw, M, 2 * C, C, 2 * C, C, C, colsum=gkvb, partials=self.S.tn_partials(), defer_fold=_DEFER_FOLD)
+            ops.gemm_tn(dkv, bs["xn1"], gkvw, M, 2 * C, C, 2 * C, C, C, colsum=gkvb, **self.tn())
             ops.gemm_nt(dkv, wkvT, dxn1, M, C, 2 * C, 2 * C, 2 * C, C, R=dxn1)
         # the block below (processed next) scales this gradient by its own MLP-branch DropPath factor first thing when its MLP is not the
         # fused kernel (stages 3-4): norm1's backward writes that scaled copy in the same pass
         prev = self.saved[i]["blocks"][j - 1] if j > 0 else None
-        pre = prev is not None and not prev.get("fused_mlp", True) and prev.get("s2") is not None and not _NO_DX2
+        pre = prev is not None and not prev.get("fused_mlp", True) and prev.get("s2") is not None
         self._dy2_pre = _empty((M, C), dx.dtype, dev) if pre else None
         ops.layernorm_bwd(dxn1, bs["x"], dx, self.f32(p + "norm1.weight"), bs["m1"], bs["r1"], M, C, C, C, C,
                           dgamma=self.gl(p + "norm1.weight"), dbeta=self.gl(p + "norm1.bias"), **self.lnk(), accumulate=True,
@@ -830,7 +779,7 @@ def _mlm_decoder_bwd(model, dl, t, sv_t, e, sv_e, A, a_map, R, lda, dA, c_map=No
     # the first writer of the word table's gradient in a pass (bert_embed_bwd adds its lookup rows at the very end): when begin_backward zeroed the whole buffer for THIS
     # pass the 23 M outputs are stored, not added by atomics (mvlt_gemm_tn_args.c_overwrite; a pass that accumulates onto earlier gradients keeps the atomics)
     ops.gemm_tn(dl, t, S.grad(wname), R, VOCAB, Hd, VOCAB_LD, Hd, Hd, colsum=S.grad("mlm_head.bias"),
-                overwrite=dt == torch.bfloat16 and S.all_zeroed_this_pass and wname not in S.touched_this_pass and not _NO_OVERWRITE)
+                overwrite=dt == torch.bfloat16 and S.all_zeroed_this_pass and wname not in S.touched_this_pass)
     S.touched_this_pass.add(wname)
     wT = S.extra[wname + "::T"]                                   # [768, VOCAB_LD], zero padded
     if dt == torch.bfloat16:
@@ -966,7 +915,7 @@ def run_forward(model, images, ids, mlm_labels=None, mlm_positions=None, mlm_cou
             raise NotImplementedError("MIM decoder backward with eval-mode BatchNorm is not scheduled (no reference config needs it)")
         sides = tuple(grids[1:])                      # the (h, w) grids of the three pyramid levels the decoder reads
         fuse_loss = (t2i_target is not None and t2i_target.dtype == torch.float32 and t2i_target.shape == (B, 3, 8 * sides[0][0], 8 * sides[0][1])
-                     and ops.upsample_l1_ok(sides[0][1], 8) and not _NO_T2I_FUSE)
+                     and ops.upsample_l1_ok(sides[0][1], 8))
         if fuse_loss:
             out["t2i_loss"] = mim_head(model, x2, x3, x4, sides, grad_on, sink, t2i_target.contiguous())
         else:

@@ -604,6 +604,21 @@ def test_tools_index_lists_every_script():
     assert not missing, missing
 
 
+def test_product_path_reads_only_the_three_kept_environment_switches():
+    """the A/B switches of rounds 1-6 were retired by their default values; what mvlt_amd/ still reads from the environment is the library override, the
+    forced collectives of the dist tests / bench.py and the bf16 gradient payload.  Text only: a new switch has to be added here on purpose."""
+    pkg = os.path.join(ROOT, "mvlt_amd")
+    names = set()
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            text = open(os.path.join(d, f), errors="ignore").read() if f.endswith((".py", ".hip", ".h", ".inc", ".cpp")) else ""
+            if f.endswith(".py"):
+                names.update(re.findall(r"""os\.environ(?:\.get\(|\[)\s*["']([^"']+)["']""", text))
+            elif os.path.basename(d) == "csrc":
+                names.update(re.findall(r"""getenv\(\s*"([^"]+)"\s*\)""", text))
+    assert {n for n in names if n.startswith("MVLT_")} == {"MVLT_HIP_LIB", "MVLT_DP_FORCE_COLLECTIVES", "MVLT_DP_BF16"}, sorted(names)
+
+
 def test_timm_create_model_path(tmp_path):
     """reference main_vl.py:25 + :259-270: `from libs import utils, pvlt` registers the factories in timm's registry as an import side effect and
     `timm.models.create_model(args.model, pretrained=True, num_classes=1000, drop_rate=, drop_path_rate=, drop_block_rate=None, token_hidden_size=,

@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mvlt_amd import ops
 dev = torch.device('cuda:0'); bf = torch.bfloat16
 def timeit(fn, reps=10):
@@ -17,4 +17,4 @@ do, dq = torch.randn(B, N, C, device=dev).to(bf), torch.empty_like(q)
 dkv = torch.zeros(B, M, 2 * C, device=dev)
 ops.sr_attention_fwd(q, kv, o, lse, B, H, N, M, C, 2 * C, C, 0, C, 0.125)
 tb = timeit(lambda: ops.sr_attention_bwd(q, kv, o, do, lse, dq, dkv, B, H, N, M, C, 2 * C, C, 2 * C, 0, C, 0.125))
-print('NQ', os.environ.get('MVLT_ATTN_BWD_NQ'), 'stage-1 bwd %.1f us' % (tb * 1e3))
+print('NQ', ops.sr_attention_bwd_chunks(B, H, N, M, torch.float32), 'stage-1 bwd %.1f us' % (tb * 1e3))

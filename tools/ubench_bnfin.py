@@ -1,4 +1,4 @@
-"""BatchNorm finalize + normalise in one launch (mvlt_bn_finalize_norm) at the MIM decoder's shapes; MVLT_BN_FIN_CAP = workgroup cap of the launch."""
+"""BatchNorm finalize + normalise in one launch (mvlt_bn_finalize_norm) at the MIM decoder's shapes."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mvlt_amd import ops

@@ -1,5 +1,4 @@
 """conv3x3 weight-gradient microbench on the eleven MIM-decoder convolutions of pvlt_tiny at batch 256 (256 px):
-    MVLT_NO_CONV_WGRAD=1 python tools/ubench_convw.py     # generic gathered TN GEMM
     python tools/ubench_convw.py                          # conv3_wgrad_kernel (LDS halo)"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,7 +19,7 @@ for side, cin, cout, tok, cnt in ((32, 192, 192, 1024, 2), (32, 64, 64, 1024, 2)
     M = B * side * side
     x = torch.randn(B, tok, cin, device=dev).to(bf); dz = torch.randn(M, cout, device=dev).to(bf)
     dW = torch.zeros(cout, 9 * cin, device=dev)
-    scr = torch.empty(512 * 65536, device=dev, dtype=bf)      # mvlt_gemm_tn_args.partials: bf16 partial blocks + ordered fold (MVLT_TN_P8=0: fp32 atomics)
+    scr = torch.empty(512 * 65536, device=dev, dtype=bf)      # mvlt_gemm_tn_args.partials: bf16 partial blocks + ordered fold
     t = timeit(lambda: ops.gemm_tn(dz, x, dW, M, cout, 9 * cin, cout, cin, 9 * cin, b_map=conv3map(side, side, tok, cin), partials=scr))
     tot += cnt * t
     print(f'{side}x{side} {cin:>3}->{cout:<3} x{cnt}: {t*1e3:7.1f} us  {2.0*M*cout*9*cin/t/1e9:6.0f} TF/s')

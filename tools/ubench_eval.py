@@ -1,5 +1,5 @@
 """Inference forward (model.eval(), no_grad) of the pre-train model at batch 256: with the MIM decoder's BatchNorms folded into their convs
-(default) and with the separate normalisation pass (MVLT_MIM_NO_BN_FOLD semantics, toggled in-process)."""
+(default) and with the separate normalisation pass (mim._NO_BN_FOLD, toggled in-process)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench

@@ -1,4 +1,4 @@
-"""A handful of NT GEMM shapes of the step, timed alone: python tools/ubench_nt_p8.py   (A/B by MVLT_NT_P8 / MVLT_HIP_LIB in separate processes)"""
+"""A handful of NT GEMM shapes of the step, timed alone: python tools/ubench_nt_p8.py   (A/B by MVLT_HIP_LIB in separate processes)"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mvlt_amd import ops

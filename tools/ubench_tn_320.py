@@ -1,5 +1,5 @@
 """The stage-3 fc weight-gradient shapes (1280 x 320 and 320 x 1280 over M rows) with partial tiles, as the step launches them: python tools/ubench_tn_320.py [M] [reps]
-(MVLT_TN_P8_320=0: the 128-wide kernel; also the target of rocprofv3 --pmc passes)."""
+(also the target of rocprofv3 --pmc passes)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mvlt_amd import ops

@@ -1,4 +1,4 @@
-"""The weight-gradient GEMMs that reduce through bf16 partial tiles + an ordered fold (default when a scratch is passed) against the fp32 atomics (MVLT_TN_P8=0),
+"""The weight-gradient GEMMs that reduce through bf16 partial tiles + an ordered fold (taken when a scratch is passed) against the fp32 atomics (no scratch),
 on the stage-4 / stage-3 MLP weight-gradient shapes: accuracy against an fp32 reference, bit-identical second launch, time."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,7 +15,7 @@ def timeit(fn, reps=20):
 for M, N1, N2 in ((49152, 512, 2048), (49152, 2048, 512), (49152, 512, 512), (49152, 1024, 512), (98304, 1280, 320), (98304, 320, 1280)):
     A = (torch.randn(M, N1, device=dev) * 0.5).to(bf); B = (torch.randn(M, N2, device=dev) * 0.5).to(bf)
     ref = A.float().t() @ B.float()
-    scr = torch.empty(256 * 65536, device=dev, dtype=bf)      # mvlt_gemm_tn_args.partials (MVLT_TN_P8=0: ignored, fp32 atomics)
+    scr = torch.empty(256 * 65536, device=dev, dtype=bf)      # mvlt_gemm_tn_args.partials
     outs = []
     for rep in range(2):
         Cw, cs = torch.zeros(N1, N2, device=dev), torch.zeros(N1, device=dev)

@@ -1,5 +1,5 @@
 """Small weight-gradient GEMMs of the step (few k-tiles per workgroup, narrow outputs): time against the HBM time of their operands, by number of m-splits.
-    python tools/ubench_tn_smallk.py            (MVLT_TN_MINT = minimum k-tiles per split)"""
+    python tools/ubench_tn_smallk.py"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mvlt_amd import ops

@@ -1,4 +1,4 @@
-"""The MLM decoder's logits GEMM (selected rows x 30522 words x 768, fp32 logits) alone, e.g. against the ring depth: MVLT_NT_NS=3 python tools/ubench_vocab.py"""
+"""The MLM decoder's logits GEMM (selected rows x 30522 words x 768, fp32 logits) alone: python tools/ubench_vocab.py"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mvlt_amd import ops
