@@ -28,7 +28,7 @@ extern "C" {
  *   6 (round 6): mvlt_tn_fold_flush(partials, stream) / mvlt_tn_fold_discard(partials): the pending-fold table is kept per scratch (= per owner);
  *                mvlt_sr_attention_bwd_chunks(); mvlt_gemm_tn_args.c_overwrite; mvlt_mlp_args.partials / partials_bytes / defer_fold
  *   7: mvlt_sr_attention_fwd_streamed() / mvlt_sr_attention_bwd_streamed(); the SR-attention entry points take any number of keys */
-#define MVLT_ABI_VERSION 7
+#define MVLT_ABI_VERSION 8
 const char* mvlt_last_error(void);
 int mvlt_abi_version(void);
 /* the kernel instantiation the library launched last on the calling thread, as the HIP runtime names it, demangled (e.g. "void (anonymous
@@ -328,9 +328,27 @@ int mvlt_smooth_l1_bwd(const float* pred, const float* target, long n, const flo
 
 /* torch.optim.AdamW step over a flat fp32 buffer (+ optional bf16 re-cast of the updated parameters).
  * hp (device, fp32[8]) = {lr, beta1, beta2, eps, weight_decay, 1-beta1^t, 1-beta2^t, grad_scale}.
+ * gscale_dev (nullable, ABI 8): a device scalar multiplied into hp[7] once per thread -- the clip coefficient of mvlt_clip_coef; NULL = ABI 7's
+ * kernel bit for bit.
  * Replaces timm create_optimizer('adamw') stepping (reference main_vl.py:308, engine_grid_masking.py:126). */
 int mvlt_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* hp,
-                    const uint8_t* decay_mask /* [n] 1 = apply weight decay (NULL = all), timm's no-decay split */, void* stream);
+                    const uint8_t* decay_mask /* [n] 1 = apply weight decay (NULL = all), timm's no-decay split */,
+                    const float* gscale_dev, void* stream);
+
+/* Gradient clipping on the flat gradient buffer (ABI 8).  Replaces the torch.nn.utils.clip_grad_norm_(parameters, clip_grad) that timm's NativeScaler
+ * runs inside loss_scaler(..., clip_grad=max_norm, parameters=model.parameters()) at reference engine_grid_masking.py:126 (--clip-grad, main_vl.py:62,434):
+ * ATen's multi-tensor norm + stack + norm of norms + a read-modify-write pass over every gradient.
+ * mvlt_grad_sumsq: n_partials workgroups (1..1024); workgroup b sums g[i]^2 over an element set fixed by (b, n_partials, n) -- only elements whose mask
+ *   byte is 1 when mask (one byte per element, nullable) is given -- and STORES partials[b] (0 when it owns nothing: no pre-zeroing).  No atomics:
+ *   bit-identical from run to run.  n % 4 == 0, g 16-byte aligned, mask 4-byte aligned.
+ * mvlt_clip_coef: one workgroup folds the partials in a fixed order; out[0] = total_norm = grad_scale * sqrt(sum) (grad_scale = the factor still owed
+ *   to g, 1/world: the norm of the MEAN gradient), out[1] = min(1, max_norm / (total_norm + 1e-6)) -- torch's formula, error_if_nonfinite=False: a
+ *   non-finite norm gives what torch gives (0 for inf, NaN for NaN).  The coefficient is then mvlt_adamw_step's gscale_dev: g is never rewritten.
+ * mvlt_scale_by_dev: x[i] *= factor_dev[0] for readers that need the clipped gradients in memory; a factor of exactly 1 skips the pass (decided on the
+ *   device).  n % 4 == 0, x 16-byte aligned. */
+int mvlt_grad_sumsq(const float* g, long n, const uint8_t* mask, float* partials, int n_partials, void* stream);
+int mvlt_clip_coef(const float* partials, int n_partials, float grad_scale, float max_norm, float* out /* fp32[2] */, void* stream);
+int mvlt_scale_by_dev(float* x, long n, const float* factor_dev, void* stream);
 int mvlt_cast_bf16(const float* src, void* dst, long n, void* stream);
 /* out[row,:] = x[row,:] * scale[row / rows_per_scale] over contiguous [M, C]: the per-sample DropPath factor applied to a
  * block's incoming gradient before its branch GEMMs (timm drop_path backward, reference libs/pvlt.py:133-134). */

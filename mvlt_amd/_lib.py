@@ -107,7 +107,7 @@ class MlpArgs(C.Structure):
 lib.mvlt_last_error.restype = C.c_char_p
 lib.mvlt_last_kernel.restype = C.c_char_p
 lib.mvlt_sizeof.argtypes = [C.c_char_p]
-ABI_VERSION = 7          # include/mvlt_hip.h MVLT_ABI_VERSION this binding was written against
+ABI_VERSION = 8          # include/mvlt_hip.h MVLT_ABI_VERSION this binding was written against
 if lib.mvlt_abi_version() != ABI_VERSION:
     raise ImportError(f"ABI mismatch: {LIB_PATH} is version {lib.mvlt_abi_version()}, the binding is version {ABI_VERSION} (stale build? run python -m mvlt_amd.build)")
 for _name, _cls in (("mvlt_rowmap", RowMap), ("mvlt_prep_desc", PrepDesc), ("mvlt_gemm_nt_args", GemmNTArgs), ("mvlt_gemm_tn_args", GemmTNArgs),
@@ -126,7 +126,7 @@ EXPORTS = ["mvlt_last_error", "mvlt_last_kernel", "mvlt_abi_version", "mvlt_size
            "mvlt_grid_mask_flags", "mvlt_grid_mask_apply", "mvlt_token_mask", "mvlt_resize_bilinear_tokens", "mvlt_resize_bilinear_tokens_multi", "mvlt_gelu_bwd",
            "mvlt_keep_mask", "mvlt_droppath_scales", "mvlt_loss_compose", "mvlt_add_column_sums",
            "mvlt_upsample_l1_fwd", "mvlt_upsample_l1_bwd", "mvlt_tn_fold_flush", "mvlt_tn_fold_discard", "mvlt_sr_attention_bwd_chunks",
-           "mvlt_sr_attention_fwd_streamed", "mvlt_sr_attention_bwd_streamed"]
+           "mvlt_sr_attention_fwd_streamed", "mvlt_sr_attention_bwd_streamed", "mvlt_grad_sumsq", "mvlt_clip_coef", "mvlt_scale_by_dev"]
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 

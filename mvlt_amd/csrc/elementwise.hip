@@ -427,9 +427,12 @@ __global__ __launch_bounds__(NT) void smooth_l1_grad_kernel(const float* pred, c
 // torch.optim.AdamW semantics (reference main_vl.py:308 via timm create_optimizer): decoupled weight decay,
 // bias-corrected moments.  lr / step-dependent scalars come from a small device array so that a captured graph replays.
 // hp = {lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale}
+// gscale_dev (nullable): one more factor on every gradient, read from the device -- the clip coefficient mvlt_clip_coef left there -- folded
+// into hp[7] once per thread; null = the kernel of ABI 7, bit for bit.
 __global__ __launch_bounds__(NT) void adamw_kernel(float* p, const float* g, float* m, float* v, bf16* p16, long n, const float* hp,
-                                                   const uint8_t* decay_mask) {
-  const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], bc1 = hp[5], bc2 = hp[6], gs = hp[7];
+                                                   const uint8_t* decay_mask, const float* gscale_dev) {
+  const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], bc1 = hp[5], bc2 = hp[6];
+  const float gs = gscale_dev ? hp[7] * gscale_dev[0] : hp[7];
   const float step_size = lr / bc1;
   const float inv_sqrt_bc2 = rsqrtf(bc2);
   for (long i = ((long)blockIdx.x * NT + threadIdx.x) * 4; i < n; i += (long)gridDim.x * NT * 4) {
@@ -450,6 +453,81 @@ __global__ __launch_bounds__(NT) void adamw_kernel(float* p, const float* g, flo
       bf16x4 o = {(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
       *(bf16x4*)(p16 + i) = o;
     }
+  }
+}
+
+// ------------------------------------------------------------------ gradient clipping over the flat gradient buffer: global norm in one read, no atomics
+// (torch.nn.utils.clip_grad_norm_ as timm's NativeScaler runs it at reference engine_grid_masking.py:126).  Workgroup b owns the 16-byte vectors
+// b * NT + t + k * gridDim.x * NT (t = lane, k = 0, 1, ...): a set fixed by (b, gridDim.x, n), summed in a fixed order -- per lane in runs of at most 35 vectors
+// (8 batches of four loads in flight, or a tail of up to three) that are folded into a second accumulator, then the 4 components, the xor butterfly of the
+// wave, the NT / 64 waves -- and stored to partials[b] with a plain store (0 when the workgroup owns nothing): bit-identical from run to run.
+// mask (nullable): one byte per element, only elements whose byte is 1 count (whatever the others hold, NaN included).
+template <bool MASK>
+__device__ __forceinline__ void sumsq_acc(f32x4& acc, f32x4 x, const uint8_t* mask, long i) {
+  if constexpr (MASK) {
+    const uint32_t mk = *(const uint32_t*)(mask + i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = ((mk >> (8 * e)) & 0xffu) == 1u ? x[e] : 0.0f;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc[e] = __builtin_fmaf(x[e], x[e], acc[e]);
+}
+template <bool MASK>
+__global__ __launch_bounds__(NT) void grad_sumsq_kernel(const float* g, long n, const uint8_t* mask, float* partials) {
+  __shared__ float s_w[NT / 64];
+  const long stride = (long)gridDim.x * NT * 4;
+  long i = ((long)blockIdx.x * NT + threadIdx.x) * 4;
+  f32x4 tot = {0.f, 0.f, 0.f, 0.f};
+  while (i < n) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    int k = 0;
+    for (; k < 8 && i + 3 * stride < n; ++k, i += 4 * stride) {          // four independent 16-byte loads in flight
+      f32x4 x[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) x[u] = *(const f32x4*)(g + i + u * stride);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) sumsq_acc<MASK>(acc, x[u], mask, i + u * stride);
+    }
+    if (k < 8)                                                           // fewer than four vectors left for this lane
+      for (; i < n; i += stride) sumsq_acc<MASK>(acc, *(const f32x4*)(g + i), mask, i);
+    tot += acc;
+  }
+  float t = wave_sum((tot[0] + tot[1]) + (tot[2] + tot[3]));
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    t = 0.f;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) t += s_w[w];
+    partials[blockIdx.x] = t;
+  }
+}
+// out[0] = total_norm = grad_scale * sqrt(sum of the partials), out[1] = min(1, max_norm / (total_norm + 1e-6)): clip_grad_norm_'s coefficient
+// (error_if_nonfinite=False: an infinite norm gives 0, a NaN norm gives NaN, as torch.clamp(max=1) does).  One workgroup, fixed order.
+__global__ __launch_bounds__(NT) void clip_coef_kernel(const float* partials, int n_partials, float grad_scale, float max_norm, float* out) {
+  __shared__ float s_w[NT / 64];
+  float t = 0.f;
+  for (int i = threadIdx.x; i < n_partials; i += NT) t += partials[i];
+  t = wave_sum(t);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    t = 0.f;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) t += s_w[w];
+    const float norm = __fmul_rn(grad_scale, sqrtf(t));                  // (rounded before the 1e-6 is added, like torch's fp32 tensor)
+    const float coef = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));
+    out[0] = norm;
+    out[1] = coef > 1.0f ? 1.0f : coef;                                  // keeps a NaN (fminf would drop it)
+  }
+}
+// x[i] *= factor_dev[0].  A factor of exactly 1 (the clip did not bite) skips the pass: decided on the device, the same for every lane; x * 1.0f == x bit for bit.
+__global__ __launch_bounds__(NT) void scale_by_dev_kernel(float* x, long n, const float* factor_dev) {
+  const float f = factor_dev[0];
+  if (f == 1.0f) return;
+  for (long i = ((long)blockIdx.x * NT + threadIdx.x) * 4; i < n; i += (long)gridDim.x * NT * 4) {
+    const f32x4 v = *(const f32x4*)(x + i);
+    *(f32x4*)(x + i) = f32x4{v[0] * f, v[1] * f, v[2] * f, v[3] * f};
   }
 }
 
@@ -898,11 +976,33 @@ extern "C" int mvlt_smooth_l1_bwd(const float* pred, const float* target, long n
 }
 
 extern "C" int mvlt_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* hp,
-                               const uint8_t* decay_mask, void* stream) {
+                               const uint8_t* decay_mask, const float* gscale_dev, void* stream) {
   MVLT_REQUIRE(p && g && m && v && hp && n >= 0 && n % 4 == 0, "mvlt_adamw_step: bad arguments (n must be a multiple of 4)");
   if (n == 0) return MVLT_OK;
-  MVLT_LAUNCH(adamw_kernel, dim3(grid_for(n / 4, 8192)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, hp, decay_mask);
+  MVLT_LAUNCH(adamw_kernel, dim3(grid_for(n / 4, 8192)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, hp, decay_mask, gscale_dev);
   return mvlt_check_launch("mvlt_adamw_step");
+}
+
+extern "C" int mvlt_grad_sumsq(const float* g, long n, const uint8_t* mask, float* partials, int n_partials, void* stream) {
+  MVLT_REQUIRE(g && partials && n >= 0 && n % 4 == 0, "mvlt_grad_sumsq: bad arguments (n must be a multiple of 4)");
+  MVLT_REQUIRE(n_partials >= 1 && n_partials <= 1024, "mvlt_grad_sumsq: n_partials must be in [1, 1024], got %d", n_partials);
+  MVLT_REQUIRE(((uintptr_t)g & 15) == 0 && ((uintptr_t)mask & 3) == 0, "mvlt_grad_sumsq: g must be 16-byte aligned, mask 4-byte aligned");
+  if (mask) MVLT_LAUNCH((grad_sumsq_kernel<true>), dim3(n_partials), dim3(NT), 0, (hipStream_t)stream, g, n, mask, partials);
+  else MVLT_LAUNCH((grad_sumsq_kernel<false>), dim3(n_partials), dim3(NT), 0, (hipStream_t)stream, g, n, mask, partials);
+  return mvlt_check_launch("mvlt_grad_sumsq");
+}
+
+extern "C" int mvlt_clip_coef(const float* partials, int n_partials, float grad_scale, float max_norm, float* out, void* stream) {
+  MVLT_REQUIRE(partials && out && n_partials >= 1 && n_partials <= 1024, "mvlt_clip_coef: bad arguments (n_partials must be in [1, 1024])");
+  MVLT_LAUNCH(clip_coef_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, partials, n_partials, grad_scale, max_norm, out);
+  return mvlt_check_launch("mvlt_clip_coef");
+}
+
+extern "C" int mvlt_scale_by_dev(float* x, long n, const float* factor_dev, void* stream) {
+  MVLT_REQUIRE(x && factor_dev && n >= 0 && n % 4 == 0 && ((uintptr_t)x & 15) == 0, "mvlt_scale_by_dev: bad arguments (n must be a multiple of 4, x 16-byte aligned)");
+  if (n == 0) return MVLT_OK;
+  MVLT_LAUNCH(scale_by_dev_kernel, dim3(grid_for(n / 4, 8192)), dim3(NT), 0, (hipStream_t)stream, x, n, factor_dev);
+  return mvlt_check_launch("mvlt_scale_by_dev");
 }
 
 extern "C" int mvlt_cast_bf16(const float* src, void* dst, long n, void* stream) {

@@ -199,7 +199,7 @@ L.lib.mvlt_gather_rows.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]
 L.lib.mvlt_scatter_rows.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]
 L.lib.mvlt_cross_entropy_fwd.argtypes = [_vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _vp]
 L.lib.mvlt_cross_entropy_bwd.argtypes = [_vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]
-L.lib.mvlt_adamw_step.argtypes = [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp]
+L.lib.mvlt_adamw_step.argtypes = [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp]
 L.lib.mvlt_cast_bf16.argtypes = [_vp, _vp, _l, _vp]
 L.lib.mvlt_transpose_cast.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp]
 
@@ -283,10 +283,41 @@ def cross_entropy_bwd(logits, labels, lse, gscale, count, dlogits, rows, V, ld, 
                                        DT[logits.dtype], DT[dlogits.dtype], stream_ptr()), "mvlt_cross_entropy_bwd")
 
 
-def adamw_step(p, g, m, v, p16, n, hp, decay_mask=None):
+def adamw_step(p, g, m, v, p16, n, hp, decay_mask=None, *, gscale_dev=None):
+    """gscale_dev: fp32 device scalar multiplied into hp[7] inside the kernel (the clip coefficient of `clip_coef`); None = no extra factor"""
     _need_cuda(p, g, m, v, hp)
     assert decay_mask is None or decay_mask.dtype == torch.uint8
-    check(L.lib.mvlt_adamw_step(_p(p), _p(g), _p(m), _p(v), _p(p16), n, _p(hp), _p(decay_mask), stream_ptr()), "mvlt_adamw_step")
+    if gscale_dev is not None:
+        _need_cuda(gscale_dev)
+        assert gscale_dev.dtype == torch.float32
+    check(L.lib.mvlt_adamw_step(_p(p), _p(g), _p(m), _p(v), _p(p16), n, _p(hp), _p(decay_mask), _p(gscale_dev), stream_ptr()), "mvlt_adamw_step")
+
+
+L.lib.mvlt_grad_sumsq.argtypes = [_vp, _l, _vp, _vp, _i, _vp]
+L.lib.mvlt_clip_coef.argtypes = [_vp, _i, _f, _f, _vp, _vp]
+L.lib.mvlt_scale_by_dev.argtypes = [_vp, _l, _vp, _vp]
+
+
+def grad_sumsq(g, n, mask, partials):
+    """partials[b] = sum of g[i]^2 over workgroup b's fixed share of g[0:n] (only where mask == 1 when a uint8 mask is given): no atomics, every entry stored"""
+    _need_cuda(g, partials)
+    assert g.dtype == torch.float32 and partials.dtype == torch.float32 and g.is_contiguous() and partials.is_contiguous()
+    assert g.numel() >= n and (mask is None or (mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and mask.numel() >= n))
+    check(L.lib.mvlt_grad_sumsq(_p(g), n, _p(mask), _p(partials), partials.numel(), stream_ptr()), "mvlt_grad_sumsq")
+
+
+def clip_coef(partials, grad_scale, max_norm, out):
+    """out[0] = grad_scale * sqrt(sum(partials)), out[1] = min(1, max_norm / (out[0] + 1e-6)) (torch.nn.utils.clip_grad_norm_'s coefficient)"""
+    _need_cuda(partials, out)
+    assert partials.dtype == torch.float32 and out.dtype == torch.float32 and out.numel() >= 2 and out.is_contiguous() and partials.is_contiguous()
+    check(L.lib.mvlt_clip_coef(_p(partials), partials.numel(), float(grad_scale), float(max_norm), _p(out), stream_ptr()), "mvlt_clip_coef")
+
+
+def scale_by_dev(x, n, factor_dev):
+    """x[0:n] *= factor_dev[0] (an fp32 device scalar; exactly 1 skips the pass on the device)"""
+    _need_cuda(x, factor_dev)
+    assert x.dtype == torch.float32 and factor_dev.dtype == torch.float32 and x.is_contiguous() and x.numel() >= n
+    check(L.lib.mvlt_scale_by_dev(_p(x), n, _p(factor_dev), stream_ptr()), "mvlt_scale_by_dev")
 
 
 L.lib.mvlt_smooth_l1_fwd.argtypes = [_vp, _vp, _l, _vp, _vp]

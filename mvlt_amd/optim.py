@@ -21,7 +21,9 @@ def phased_ranges(S):
     With them (mvlt_amd.dist.DataParallel hands them over un-waited when this optimizer is the next reader): first the ranges whose collectives were
     issued DURING the backward pass -- by now (mostly) complete -- then the ones issued at its end, each group after `wait()` on its works (a
     stream-side wait for RCCL: the host keeps enqueuing).  The first launch then runs while the tail is still on the wire; element-wise AdamW makes the
-    result bit-identical to one launch over everything.  Anything the collectives do not cover exactly once falls back to wait-all + one range."""
+    result bit-identical to one launch over everything.  Anything the collectives do not cover exactly once falls back to wait-all + one range.
+    With a clip pending (FlatStore.clip_grad_norm ran: the global norm needs every gradient) the collectives are already waited and this yields the
+    single whole range."""
     works, S.grad_works = S.grad_works, []
     if not works:
         yield 0, S.total
@@ -48,6 +50,17 @@ def phased_ranges(S):
                 merged.append([lo, hi])
         for lo, hi in merged:
             yield lo, hi
+
+
+def clip_grad_norm_(model, max_norm):
+    """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) for loops that do not go through engine.BF16Scaler: the global norm in one pass
+    over the flat gradient buffer (FlatStore.clip_grad_norm), then settled at once -- G is scaled in place by the coefficient and by an owed 1/world,
+    so `.grad`, logging and any optimizer see final, clipped gradients.  `model`: the model, a DataParallel / DDP wrapper around it, or its store.
+    Returns the total norm as a 0-dim device tensor (no host read)."""
+    S = model if hasattr(model, "clip_grad_norm") else _unwrap(model).store
+    norm = S.clip_grad_norm(max_norm).clone()           # (the store's own scalar is overwritten by the next clipping)
+    S.apply_pending_scale()
+    return norm
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -107,6 +120,7 @@ class FusedAdamW(torch.optim.Optimizer):
         b1, b2 = g0["betas"]
         assert g0["lr"] == g1["lr"], "FusedAdamW steps both param groups with one learning rate (as timm's scheduler sets them)"
         gscale, S.pending_grad_scale = S.pending_grad_scale, 1.0      # 1/world of the data-parallel mean, applied in the kernel
+        clip, S.pending_clip = S.pending_clip, None                   # clip coefficient (device scalar) of FlatStore.clip_grad_norm: one more factor in the kernel
         row = [g0["lr"], b1, b2, g0["eps"], g1["weight_decay"], 1 - b1 ** self._step, 1 - b2 ** self._step, gscale]
         if self._hp_pin is None:
             self._hp.copy_(torch.tensor(row, dtype=torch.float32))
@@ -119,7 +133,8 @@ class FusedAdamW(torch.optim.Optimizer):
             ev = self._hp_ev[k] = self._hp_ev[k] or torch.cuda.Event()
             ev.record()
         for lo, hi in phased_ranges(S):
-            ops.adamw_step(S.P[lo:hi], S.G[lo:hi], self._m[lo:hi], self._v[lo:hi], None if S.C is None else S.C[lo:hi], hi - lo, self._hp, self._wd_mask[lo:hi])
+            ops.adamw_step(S.P[lo:hi], S.G[lo:hi], self._m[lo:hi], self._v[lo:hi], None if S.C is None else S.C[lo:hi], hi - lo, self._hp, self._wd_mask[lo:hi],
+                           gscale_dev=clip)
         # W^T / permuted conv operand copies are refreshed by the next forward; the plain bf16 copy S.C is already current,
         # which holds as long as nothing else writes the parameters before that forward (FlatStore.versions() notices)
         S.force_dirty = True

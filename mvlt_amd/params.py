@@ -145,6 +145,8 @@ class FlatStore:
         self.touched_this_pass = set()           # gradient slices a kernel of the running pass has written (first writers may store instead of add)
         self.scale_in_optimizer = False   # set by engine.BF16Scaler around backward + FusedAdamW.step: that kernel applies `pending_grad_scale`
         self.pending_grad_scale = 1.0     # factor still owed to G (1/world after a data-parallel SUM all-reduce)
+        self.pending_clip = None          # clip coefficient still owed to G: a 1-element fp32 DEVICE tensor (clip_grad_norm), applied by FusedAdamW's kernel
+        self._clip = None                 # (key, norm mask, partials, [norm, coef]) of clip_grad_norm, allocated once per store
         # gradient collectives still in flight when the backward pass returned: [(work, lo, hi, g_view, payload or None, early)].  Only set while
         # `scale_in_optimizer` (the fused optimizer is the next reader: it steps the ranges whose collectives are done while the tail is on the
         # wire, FusedAdamW.step); every other reader of G goes through wait_grads() first.
@@ -345,6 +347,7 @@ class FlatStore:
         if not any(alias):
             self.G.zero_()
             self.pending_grad_scale = 1.0
+            self.pending_clip = None           # a clip nobody stepped belongs to gradients that are gone
         else:
             # mixed state (a zero_grad over a subset of the parameters, or p.grad = None on some): decided per parameter, like torch --
             # the slices whose .grad aliases keep their running sum, the others start from zero (the any-alias rule of round 3
@@ -557,11 +560,53 @@ class FlatStore:
                 g.copy_(t)
 
     def apply_pending_scale(self):
-        """make G itself carry the owed factor (anything that READS gradients before the optimizer step: clipping, logging)"""
+        """make G itself carry the owed factors -- the 1/world and a pending clip coefficient (anything that READS gradients before the optimizer
+        step: logging, a stock optimizer, a second clipping)"""
         self.wait_grads()
         if self.pending_grad_scale != 1.0:
             self.G.mul_(self.pending_grad_scale)
             self.pending_grad_scale = 1.0
+        if self.pending_clip is not None:
+            clip, self.pending_clip = self.pending_clip, None
+            ops.scale_by_dev(self.G, self.total, clip)      # (skips the pass on the device when the clip did not bite)
+
+    # ---- gradient clipping on the flat buffer ------------------------------------------------------------------------------
+    CLIP_PARTIALS = 1024          # workgroups of the sum-of-squares launch (4 per CU: 40 M gradients = 39 16-byte loads per lane)
+
+    def _clip_buffers(self):
+        """(norm mask, partials, [norm, coef]): the mask holds 1 exactly for the elements of parameters with requires_grad=True -- what
+        clip_grad_norm_(model.parameters()) sees (it skips `.grad is None`, which is what a frozen parameter keeps; the tied decoder weight is one entry
+        of the store) -- and 0 for frozen parameters and the alignment gaps.  Always passed: nothing promises that the gaps of G hold zeros (a caller
+        may write G through the flat view).  Rebuilt when the store was re-materialized or a parameter was (un)frozen."""
+        key = (self.G.data_ptr(), tuple(p.requires_grad for p in self._plist))
+        if self._clip is None or self._clip[0] != key:
+            mask = torch.zeros(self.total, dtype=torch.uint8)
+            for name, p in self.params.items():
+                if p.requires_grad:
+                    off, n, _ = self.offsets[name]
+                    mask[off:off + n] = 1
+            dev = self.G.device
+            old = self._clip
+            part = old[2] if old is not None and old[2].device == dev else torch.empty(self.CLIP_PARTIALS, device=dev, dtype=torch.float32)
+            out = old[3] if old is not None and old[3].device == dev else torch.zeros(2, device=dev, dtype=torch.float32)
+            self._clip = (key, mask.to(dev), part, out)
+        return self._clip[1:]
+
+    @torch.no_grad()
+    def clip_grad_norm(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) without rewriting G and without a host read: one pass over G for the global
+        norm (of the MEAN gradient: `pending_grad_scale` is part of it and stays owed), the coefficient min(1, max_norm / (norm + 1e-6)) left on the
+        device as `pending_clip` for FusedAdamW's kernel -- or for apply_pending_scale(), if someone else reads the gradients first.  Returns the
+        norm as a 0-dim device tensor (a view of the store's persistent [norm, coef] pair: the next call overwrites it)."""
+        self.wait_grads()
+        self.sync_grads()
+        if self.pending_clip is not None:                   # a second clipping sees the gradients the first one left
+            self.apply_pending_scale()
+        mask, part, out = self._clip_buffers()
+        ops.grad_sumsq(self.G, self.total, mask, part)
+        ops.clip_coef(part, self.pending_grad_scale, max_norm, out)
+        self.pending_clip = out[1:2]
+        return out[0]
 
     def sync_grads(self):
         """Make G the truth for every parameter (flat-buffer optimizers call this before stepping): gradients that
