@@ -330,9 +330,17 @@ int mvlt_smooth_l1_bwd(const float* pred, const float* target, long n, const flo
  * hp (device, fp32[8]) = {lr, beta1, beta2, eps, weight_decay, 1-beta1^t, 1-beta2^t, grad_scale}.
  * gscale_dev (nullable, ABI 8): a device scalar multiplied into hp[7] once per thread -- the clip coefficient of mvlt_clip_coef; NULL = ABI 7's
  * kernel bit for bit.
+ * decay_mask (nullable, one byte per element; NULL = every element 1):
+ *   0                      step, no weight decay (timm's no-decay split: 1-D tensors and biases)
+ *   1                      step with weight decay
+ *   2 = MVLT_ADAMW_FROZEN  frozen (requires_grad=False): p, m, v and p_bf16 are NOT written, and g / m / v of the element reach nothing (a NaN or
+ *                          Inf there is harmless).  A 16-byte vector whose four bytes are all 2 is skipped after the mask read: no load, no store.
+ *   A new value of the byte, not a new signature: the ABI version stays 8, and a NULL mask or a mask of 0s and 1s gives the results it always gave,
+ *   bit for bit.
  * Replaces timm create_optimizer('adamw') stepping (reference main_vl.py:308, engine_grid_masking.py:126). */
+#define MVLT_ADAMW_FROZEN 2
 int mvlt_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* hp,
-                    const uint8_t* decay_mask /* [n] 1 = apply weight decay (NULL = all), timm's no-decay split */,
+                    const uint8_t* decay_mask /* [n] 0 / 1 / MVLT_ADAMW_FROZEN, see above */,
                     const float* gscale_dev, void* stream);
 
 /* Gradient clipping on the flat gradient buffer (ABI 8).  Replaces the torch.nn.utils.clip_grad_norm_(parameters, clip_grad) that timm's NativeScaler

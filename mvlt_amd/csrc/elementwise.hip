@@ -429,6 +429,11 @@ __global__ __launch_bounds__(NT) void smooth_l1_grad_kernel(const float* pred, c
 // hp = {lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, grad_scale}
 // gscale_dev (nullable): one more factor on every gradient, read from the device -- the clip coefficient mvlt_clip_coef left there -- folded
 // into hp[7] once per thread; null = the kernel of ABI 7, bit for bit.
+// Mask byte 2 (MVLT_ADAMW_FROZEN): the element belongs to a parameter with requires_grad=False -- p, m, v and the bf16 copy are not written and
+// nothing of g / m / v is used.  The four mask bytes of a 16-byte vector are read FIRST: an all-frozen vector (the 23 M-element word table of a
+// fine-tune run) costs that one read -- no load of p / g / m / v, no store; a vector without a frozen byte takes the loop body it always took.
+// Parameters start at 8-element offsets, so a mixed vector exists only where a frozen tensor's ragged tail meets its alignment gap (at most one
+// per tensor): it is stepped lane by lane with scalar stores, the frozen lanes are skipped.
 __global__ __launch_bounds__(NT) void adamw_kernel(float* p, const float* g, float* m, float* v, bf16* p16, long n, const float* hp,
                                                    const uint8_t* decay_mask, const float* gscale_dev) {
   const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], bc1 = hp[5], bc2 = hp[6];
@@ -436,8 +441,10 @@ __global__ __launch_bounds__(NT) void adamw_kernel(float* p, const float* g, flo
   const float step_size = lr / bc1;
   const float inv_sqrt_bc2 = rsqrtf(bc2);
   for (long i = ((long)blockIdx.x * NT + threadIdx.x) * 4; i < n; i += (long)gridDim.x * NT * 4) {
-    f32x4 pv = *(f32x4*)(p + i), gv = *(const f32x4*)(g + i), mv = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
     const uint32_t dm = decay_mask ? *(const uint32_t*)(decay_mask + i) : 0x01010101u;   // 1 byte per parameter
+    const uint32_t fz = dm & 0x02020202u;
+    if (fz == 0x02020202u) continue;
+    f32x4 pv = *(f32x4*)(p + i), gv = *(const f32x4*)(g + i), mv = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float gr = gv[e] * gs;
@@ -448,10 +455,19 @@ __global__ __launch_bounds__(NT) void adamw_kernel(float* p, const float* g, flo
       pv[e] = pp - step_size * mm / denom;
       mv[e] = mm; vv[e] = v2;
     }
-    *(f32x4*)(p + i) = pv; *(f32x4*)(m + i) = mv; *(f32x4*)(v + i) = vv;
-    if (p16) {
-      bf16x4 o = {(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
-      *(bf16x4*)(p16 + i) = o;
+    if (fz == 0u) {
+      *(f32x4*)(p + i) = pv; *(f32x4*)(m + i) = mv; *(f32x4*)(v + i) = vv;
+      if (p16) {
+        bf16x4 o = {(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
+        *(bf16x4*)(p16 + i) = o;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if ((fz >> (8 * e)) & 2u) continue;            // (what a frozen lane computed above -- NaN included -- is dropped here)
+        p[i + e] = pv[e]; m[i + e] = mv[e]; v[i + e] = vv[e];
+        if (p16) p16[i + e] = (bf16)pv[e];
+      }
     }
   }
 }

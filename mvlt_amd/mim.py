@@ -177,9 +177,9 @@ class MimStep:
         return out
 
     # ------------------------------------------------------------------ backward
-    def bn_conv_bwd(self, name, dy, lddy, dx=None, lddx=0, accumulate=False, dx_map=None, dx_dtype=torch.float32):
+    def bn_conv_bwd(self, name, dy, lddy, dx=None, lddx=0, accumulate=False, dx_map=None, dx_dtype=torch.float32, need_dx=True):
         """dy: fp32 gradient w.r.t. the BN output [M, cout] (row stride lddy).  Accumulates the BN / conv parameter gradients
-        into the flat buffer and returns (or accumulates into) the gradient w.r.t. the conv input."""
+        into the flat buffer and returns (or accumulates into) the gradient w.r.t. the conv input (need_dx=False: parameter gradients only)."""
         S, dev, dt = self.S, self.dev, self.dt
         r = self.rec[name]
         p, M, cin, cout = r["p"], r["M"], r["cin"], r["cout"]
@@ -191,6 +191,8 @@ class MimStep:
         # wgrad computed in the gather's [out][dy][dx][cin] order, accumulated at nn.Conv2d's [out][cin][3][3] place
         from .schedule import conv_wgrad
         conv_wgrad(S, p + ".0.weight", dz, r["xin"], M, cout, 9 * cin, cout, r["ld_in"], r["amap"], 9, cin)
+        if not need_dx:
+            return None
         # dgrad: gather dz over the same grid with flipped taps
         gmap = conv3map(r["side"][0], r["side"][1], r["side"][0] * r["side"][1], cout)
         if dx is None:
@@ -199,7 +201,8 @@ class MimStep:
                     R=dx if accumulate else None)
         return dx
 
-    def backward(self, dout, sink=None):
+    def backward(self, dout, sink=None, dgrad=True):
+        """dgrad=False (nothing in the trunk is trainable): the three reductions give parameter gradients only, no gradient for x2 / x3 / x4"""
         S, dev, dt, B = self.S, self.dev, self.dt, self.B
         s1, s2, s3, M1, M2, M3 = self.s1, self.s2, self.s3, self.M1, self.M2, self.M3
         ch = 64
@@ -248,6 +251,10 @@ class MimStep:
         # reductions: gradients w.r.t. the image tokens of the stage outputs (text rows stay zero)
         grads = []
         for name, dy, x, side in (("reduction1", dlow, self.x[0], s1), ("reduction2", dmid, self.x[1], s2), ("reduction3", dhigh, self.x[2], s3)):
+            if not dgrad:
+                self.bn_conv_bwd(name, dy, ch, need_dx=False)
+                grads.append(None)
+                continue
             if name == "reduction3" and sink is not None:
                 dxs, ret = sink.take(x.shape, x.dtype, x.device)      # the heads' common buffer: image rows are this decoder's
             else:
@@ -265,13 +272,15 @@ class _MimFn(torch.autograd.Function):
         step = MimStep(model, x2, x3, x4, sides, model.training, need_grad)
         out = step.forward(target)
         ctx.step, ctx.sink = step, sink
+        plan = getattr(model, "_plan", None)
+        ctx.dgrad = plan is None or plan.by["t2i_head"].dgrad
         return out
 
     @staticmethod
     def backward(ctx, dout):
         step = ctx.step
         step.S.queue_finalize()
-        g2, g3, g4 = step.backward(dout, ctx.sink)
+        g2, g3, g4 = step.backward(dout, ctx.sink, ctx.dgrad)
         ctx.step = ctx.sink = None
         step.S.fold_copies(early=True)                # the conv weight gradients leave the tap arena for G (with a data-parallel wrapper: now)
         step.S.announce_prefix("t2i_head.")          # the decoder's gradients are final: reduce them under the trunk backward

@@ -283,8 +283,12 @@ def cross_entropy_bwd(logits, labels, lse, gscale, count, dlogits, rows, V, ld, 
                                        DT[logits.dtype], DT[dlogits.dtype], stream_ptr()), "mvlt_cross_entropy_bwd")
 
 
+ADAMW_FROZEN = 2          # decay_mask byte of a frozen element (MVLT_ADAMW_FROZEN in include/mvlt_hip.h); 0 = step, 1 = step with weight decay
+
+
 def adamw_step(p, g, m, v, p16, n, hp, decay_mask=None, *, gscale_dev=None):
-    """gscale_dev: fp32 device scalar multiplied into hp[7] inside the kernel (the clip coefficient of `clip_coef`); None = no extra factor"""
+    """decay_mask: one uint8 per element -- 0 step, 1 step with weight decay, ADAMW_FROZEN leave p / m / v / p16 alone.
+    gscale_dev: fp32 device scalar multiplied into hp[7] inside the kernel (the clip coefficient of `clip_coef`); None = no extra factor"""
     _need_cuda(p, g, m, v, hp)
     assert decay_mask is None or decay_mask.dtype == torch.uint8
     if gscale_dev is not None:

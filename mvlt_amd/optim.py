@@ -6,10 +6,15 @@ decoupled weight decay, bias-corrected moments, eps 1e-8, and timm's param-group
 get weight_decay 0, everything else args.weight_decay.  It is a torch.optim.Optimizer, so GradScaler.step(),
 lr schedulers (`param_groups[i]['lr']`) and state_dict()/load_state_dict() keep working; `param_groups[0]` is the
 no-decay group and `[1]` the decay group, like timm's add_weight_decay.
+
+Frozen parameters (requires_grad=False) are left alone, as torch.optim.AdamW leaves a parameter without `.grad` alone: the groups hold every
+parameter of the model, and the per-element mask of the kernel carries a third value for the elements of frozen ones (neither they nor their
+moments nor their bf16 copies are written).  The mask follows requires_grad from step to step, so un-freezing needs no new optimizer.
 """
 import torch
 
 from . import ops
+from .params import ALIGN
 
 
 def _unwrap(model):
@@ -68,14 +73,15 @@ class FusedAdamW(torch.optim.Optimizer):
         model = _unwrap(model)
         self.model = model
         no_decay, decay = [], []
+        # every parameter of the model is in a group, frozen ones too: `requires_grad` decides per step (the mask byte of mvlt_adamw_step), so a
+        # parameter frozen now and un-frozen later starts stepping without a new optimizer
         for name, p in model.named_parameters():
-            if not p.requires_grad:
-                continue
             (no_decay if (p.dim() == 1 or name.endswith(".bias")) else decay).append(p)
         groups = [dict(params=no_decay, weight_decay=0.0), dict(params=decay, weight_decay=weight_decay)]
         super().__init__(groups, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._step = 0
-        self._m = self._v = self._wd_mask = None
+        self._m = self._v = self._wd_mask = self._mask_key = None
+        self._frozen_ranges = []              # maximal [lo, hi) runs of the flat buffer whose every element is frozen (gaps inside a run included)
         self._hp = self._hp_pin = None
         self._hp_ev = [None] * 4
         self._pending = None                  # (m, v) of a checkpoint loaded before the flat store exists
@@ -100,15 +106,31 @@ class FusedAdamW(torch.optim.Optimizer):
             # next forward behind an idle GPU (1.3 ms per fine-tune step, tools/host_time.py).  An event per row guards its reuse.
             self._hp_pin = torch.zeros(4, 8).pin_memory() if S.P.is_cuda else None
             self._hp_ev = [None] * 4
-            # one byte per parameter: 1 = weight decay applies (timm's split: not for 1-D tensors / biases)
+        key = (S.P.data_ptr(), tuple(p.requires_grad for p in S._plist))
+        if self._mask_key != key:                # the store was re-materialised, or a parameter was frozen / un-frozen (as FlatStore's norm mask)
+            # one byte per element: 1 = weight decay applies (timm's split: not for 1-D tensors / biases), 0 = it does not (alignment gaps too),
+            # 2 = the parameter is frozen: the kernel leaves it, its moments and its bf16 copy alone
             ids_nd = {id(p) for p in self.param_groups[0]["params"]}
             mask = torch.zeros(S.total, dtype=torch.uint8)
+            runs = []
             for name, p in S.params.items():
                 off, n, _ = S.offsets[name]
-                if id(p) not in ids_nd:
+                if not p.requires_grad:
+                    mask[off:off + n] = ops.ADAMW_FROZEN
+                    hi = off + (n + ALIGN - 1) // ALIGN * ALIGN
+                    if runs and runs[-1][1] == off:
+                        runs[-1][1] = hi
+                    else:
+                        runs.append([off, hi])
+                elif id(p) not in ids_nd:
                     mask[off:off + n] = 1
             self._wd_mask = mask.to(S.P.device)
+            self._frozen_ranges = [(lo, hi) for lo, hi in runs]
+            self._mask_key = key
         return S
+
+    def _all_frozen(self, lo, hi):
+        return any(a <= lo and hi <= b for a, b in self._frozen_ranges)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -133,6 +155,8 @@ class FusedAdamW(torch.optim.Optimizer):
             ev = self._hp_ev[k] = self._hp_ev[k] or torch.cuda.Event()
             ev.record()
         for lo, hi in phased_ranges(S):
+            if self._all_frozen(lo, hi):         # nothing in the range steps: no launch
+                continue
             ops.adamw_step(S.P[lo:hi], S.G[lo:hi], self._m[lo:hi], self._v[lo:hi], None if S.C is None else S.C[lo:hi], hi - lo, self._hp, self._wd_mask[lo:hi],
                            gscale_dev=clip)
         # W^T / permuted conv operand copies are refreshed by the next forward; the plain bf16 copy S.C is already current,

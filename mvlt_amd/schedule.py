@@ -55,13 +55,131 @@ class Names:
         return f"block{i+1}.{j}."
 
 
+# =============================================================================================== backward plan (frozen parameters)
+class PlanUnit:
+    """One unit of the backward pass in the order the schedule visits it.
+    launches: {launch group -> does it run}: a parameter-gradient launch runs when ANY parameter it writes is trainable (the optimizer's mask byte
+              protects the frozen ones of a mixed launch); group "ln" are LayerNorm weights / biases, whose gradients ride in kernels that run for dx.
+    wgrad: some parameter of the unit is trainable.  dgrad: the unit's input gradient is needed (a unit visited later has a trainable parameter).
+    save: the forward keeps the unit's activations (= the backward gets as far as this unit)."""
+    __slots__ = ("name", "kind", "params", "launches", "wgrad", "dgrad", "save")
+
+    def __init__(self, name, kind, groups, live):
+        self.name, self.kind = name, kind
+        self.params = {k: tuple(v) for k, v in groups.items()}
+        self.launches = {k: any(n in live for n in v) for k, v in groups.items()}
+        self.wgrad = any(self.launches.values())
+        self.dgrad = self.save = False
+
+    def only(self, *groups):
+        """no launch group outside `groups` runs"""
+        return not any(on for k, on in self.launches.items() if k not in groups)
+
+    def __repr__(self):
+        return f"PlanUnit({self.name}: wgrad={self.wgrad} dgrad={self.dgrad} save={self.save} {self.launches})"
+
+
+class BackwardPlan:
+    """units: [PlanUnit] -- the heads (they run first: autograd orders them among themselves), then block4.<last> .. block4.0, embed4 (patch_embed4,
+    text_embed4, pos_embed4, text_pos_embed4), stage 3, 2, 1 likewise, and text_embeddings (the BERT embedding block) last.
+    cut: index of the last unit with a trainable parameter (None: nothing is trainable); no unit behind it runs or saves."""
+
+    def __init__(self, units, live):
+        self.units, self.live = units, live
+        self.by = {u.name: u for u in units}
+        on = [k for k, u in enumerate(units) if u.wgrad]
+        self.cut = on[-1] if on else None
+        trunk_on = any(u.wgrad for u in units if u.kind != "head")
+        for k, u in enumerate(units):
+            # a head's input gradient feeds the trunk only (the heads do not feed each other)
+            u.dgrad = trunk_on if u.kind == "head" else (self.cut is not None and k < self.cut)
+            u.save = u.wgrad or u.dgrad
+        self.trunk_save = any(u.save for u in units if u.kind != "head")
+
+    @property
+    def cut_unit(self):
+        return None if self.cut is None else self.units[self.cut]
+
+    def signature(self):
+        return [(u.name, u.wgrad, u.dgrad, u.save, tuple(sorted(u.launches.items()))) for u in self.units]
+
+
+class _EveryLaunch(dict):
+    def __missing__(self, k):
+        return True
+
+
+class _EveryUnit(PlanUnit):
+    """stand-in for any unit when a pass has no plan: every launch runs, everything is kept"""
+    __slots__ = ()
+
+    def __init__(self):
+        self.name, self.kind, self.params, self.launches = "*", "all", {}, _EveryLaunch()
+        self.wgrad = self.dgrad = self.save = True
+
+    def only(self, *groups):
+        return False
+
+
+_EVERY = _EveryUnit()
+WORD_TABLE = "text_embeddings.word_embeddings.weight"
+
+
+def backward_plan(model):
+    """What the backward pass of `model` runs for the parameters' current requires_grad flags.  Pure Python: reads requires_grad, depths, loss_type and
+    the parameter names only (no GPU, no flat store).  The schedule asks for it at the start of every grad-enabled forward, so freezing and un-freezing
+    between steps takes effect with the next step."""
+    names = [n for n, _ in model.named_parameters()]
+    live = frozenset(n for n, p in model.named_parameters() if p.requires_grad)
+    have = set(names)
+    lt = model.loss_type
+    units = []
+
+    def wb(prefix):
+        return [n for n in (prefix + ".weight", prefix + ".bias") if n in have]
+
+    if lt.get("mlm"):
+        units.append(PlanUnit("mlm_head", "head", dict(
+            table=[WORD_TABLE], bias=["mlm_head.bias"], dense=wb("mlm_head.transform.dense"), embed=wb("mlm_head_embed.0"),
+            ln=wb("mlm_head.transform.LayerNorm") + wb("mlm_head_embed.1")), live))
+    for h, on in (("itm", lt.get("itm")), ("sup_cls", lt.get("cls")), ("sub_cls", lt.get("cls"))):
+        if on:
+            units.append(PlanUnit(h + "_head", "head", dict(
+                linear=[h + "_head.linear.weight"], bias=[h + "_head.linear.bias", h + "_head.linear_bias"], embed=wb(h + "_head_embed.0"),
+                ln=wb(h + "_head_embed.1")), live))
+    if lt.get("t2i"):
+        units.append(PlanUnit("t2i_head", "head", dict(all=[n for n in names if n.startswith("t2i_head.")]), live))
+    for i in (4, 3, 2, 1):
+        for j in reversed(range(model.depths[i - 1])):
+            p = f"block{i}.{j}."
+            units.append(PlanUnit(f"block{i}.{j}", "block", dict(
+                fc1=wb(p + "mlp.fc1"), fc2=wb(p + "mlp.fc2"), proj=wb(p + "attn.proj"), q=wb(p + "attn.q"), kv=wb(p + "attn.kv"), sr=wb(p + "attn.sr"),
+                ln=wb(p + "norm1") + wb(p + "norm2") + wb(p + "attn.norm")), live))
+        units.append(PlanUnit(f"embed{i}", "embed", dict(
+            patch=wb(f"patch_embed{i}.proj"), text=wb(f"text_embed{i}.0"), pos=[f"pos_embed{i}", f"text_pos_embed{i}"],
+            ln=wb(f"patch_embed{i}.norm") + wb(f"text_embed{i}.1")), live))
+    units.append(PlanUnit("text_embeddings", "bert", dict(embed=[n for n in names if n.startswith("text_embeddings.")]), live))
+    return BackwardPlan(units, live)
+
+
+def _plan_for(model):
+    """backward_plan(model), cached on the store under the requires_grad tuple (~230 attribute reads per forward)"""
+    S = model.store
+    key = (id(S.P), tuple(p.requires_grad for p in S._plist))
+    hit = getattr(S, "_plan", None)
+    if hit is None or hit[0] != key:
+        hit = S._plan = (key, backward_plan(model))
+    return hit[1]
+
+
 # =============================================================================================== trunk
 class TrunkStep:
     """One forward (and optionally backward) of the 4-stage trunk."""
 
-    def __init__(self, model, images, ids, need_grad):
+    def __init__(self, model, images, ids, need_grad, plan=None):
         self.m = model
         self.S = model.store
+        self.plan = plan if need_grad else None      # BackwardPlan of this pass (None: every unit runs, as if all parameters were trainable)
         self.dev = images.device
         self.dt = model.compute_dtype       # GEMM / attention operand dtype
         self.rt = torch.float32             # residual-stream dtype: adds and LayerNorm inputs stay fp32 (what the
@@ -89,6 +207,15 @@ class TrunkStep:
             e = torch.cuda.Event(enable_timing=True)
             e.record()
             ev.append(e)
+
+    # ---- backward plan
+    def unit(self, name):
+        """the plan's unit `name`; without a plan a stand-in whose every launch runs"""
+        return self.plan.by[name] if self.plan is not None else _EVERY
+
+    def keeps(self, name):
+        """does the forward keep the activations of unit `name`"""
+        return self.need_grad and self.unit(name).save
 
     # ---- parameter access
     def w(self, name):
@@ -199,6 +326,8 @@ class TrunkStep:
         for i in range(4):
             xp, blk_index = self._stage_forward(i, xp, blk_index)
             outs.append(xp)
+            if i == 0 and not self.keeps("embed1"):
+                self.emb = self.keep = None        # read again only by stage 1's text-embedding weight gradient and the BERT block's backward
         return outs
 
     def _stage_forward(self, i, xp, blk_index):
@@ -265,6 +394,9 @@ class TrunkStep:
         if taps is not None:            # tests: stage outputs in the reference's (img_feat NCHW, text_feat) form
             taps[f"img_feat{i+1}"] = x[:, :HW].float().reshape(B, h, w, C).permute(0, 3, 1, 2)
             taps[f"text_feat{i+1}"] = x[:, HW:].float()
+        if not self.keeps(f"embed{i+1}"):       # the backward stops above this stage's embeddings (or there is none): only the shapes stay
+            for k in ("P1", "pm_in", "pe_pre", "pe_mean", "pe_rstd", "te_pre", "te_mean", "te_rstd", "x_in_prev"):
+                sv.pop(k, None)
         self.saved.append(sv)
         return x, blk_index
 
@@ -277,6 +409,7 @@ class TrunkStep:
         M = B * N
         p = Names.blk(i, j)
         f32 = torch.float32
+        keep = self.keeps(f"block{i+1}.{j}")       # (a block behind the backward plan's cut keeps nothing)
         bs = dict(x=x)
         s1, s2 = self._droppath_scales(blk_index)
         bs["s1"], bs["s2"] = s1, s2
@@ -359,13 +492,13 @@ class TrunkStep:
                         out_op=xo if last_op else None, post_ln=post)
         else:
             ops.layernorm_fwd(xm, xn2, self.f32(p + "norm2.weight"), self.f32(p + "norm2.bias"), M, C, C, C, EPS_BLOCK, mean=bs["m2"], rstd=bs["r2"])
-            hpre = _empty((M, hid), dt, dev) if self.need_grad else None
+            hpre = _empty((M, hid), dt, dev) if keep else None
             gact = _empty((M, hid), dt, dev)
             ops.gemm_nt(xn2, self.w(p + "mlp.fc1.weight"), gact, M, hid, C, C, C, hid, bias=self.f32(p + "mlp.fc1.bias"), act=1, H=hpre)
             bs["hpre"], bs["gact"] = hpre, gact
             ops.gemm_nt(gact, self.w(p + "mlp.fc2.weight"), xo, M, C, hid, hid, hid, C, bias=self.f32(p + "mlp.fc2.bias"),
                         row_scale=s2, rows_per_scale=N, R=xm)
-        if not self.need_grad:
+        if not keep:
             bs.clear()
         return xo, bs
 
@@ -387,6 +520,8 @@ class TrunkStep:
         own = [d is not None and d.dtype == dt and d.is_contiguous() and S.owns(d) for d in dxs]
         dx, merged = None, False
         for i in (3, 2, 1, 0):
+            if not self.unit(f"block{i+1}.{m.depths[i] - 1}").save:
+                break                      # the plan's cut lies above this stage: nothing from here on has a trainable parameter
             sv = self.saved[i]
             d_out = dxs[i]
             if d_out is not None and not merged:
@@ -400,8 +535,9 @@ class TrunkStep:
             # the stage's input gradient is accumulated straight into the previous stage's own head gradient where there is one
             into = dxs[i - 1] if i > 0 and own[i - 1] else None
             dx = self._stage_backward(i, sv, dx.view(B, sv["N"], sv["C"]), into)
-            merged = into is not None
-            self.S.announce_stage(i)
+            merged = into is not None and dx is not None
+            if self.unit(f"embed{i+1}").save:      # (a stage the cut ends half-way travels with the leftovers at the end of the pass)
+                self.S.announce_stage(i)
         # the learned position embeddings (root parameters: they sit in front of the stage blocks in the flat layout) got their last
         # contribution from stage 1's backward: final now, so that only the BERT embedding block is left for the end of the pass
         if self._pos_adj:
@@ -416,14 +552,24 @@ class TrunkStep:
         C, HW, N = sv["C"], sv["HW"], sv["N"]
         self._mark()
         for j in reversed(range(m.depths[i])):
+            if not self.unit(f"block{i+1}.{j}").save:        # behind the cut
+                self._mark()
+                return None
             dx = self._block_backward(i, j, sv["blocks"][j], dx)
         self._mark()
+        u = self.unit(f"embed{i+1}")
+        if not u.save:
+            return None
+        on = u.launches
         pe, ten = f"patch_embed{i+1}.", f"text_embed{i+1}."
         f32 = torch.float32
         # pos-embed / text-pos-embed gradients: sum over the batch of d(x0)
-        dpos_all = _empty((N, C), f32, dev)
-        ops.batch_sum(dx, dpos_all, B, N, C, N, C, acc2=self.g(f"text_pos_embed{i+1}")[0], split=HW)        # text rows straight into G
-        self._pos_backward(i, dpos_all[:HW])
+        if on["pos"]:
+            dpos_all = _empty((N, C), f32, dev)
+            ops.batch_sum(dx, dpos_all, B, N, C, N, C, acc2=self.g(f"text_pos_embed{i+1}")[0], split=HW)        # text rows straight into G
+            self._pos_backward(i, dpos_all[:HW])
+        if not u.dgrad and u.only("pos"):            # the cut, with the two position embeddings the only trainable tensors: the rest of the unit is dropped
+            return None
         # patch-embed LN backward -> d(pe_pre)
         d_pe = _empty((B * HW, C), dt, dev)
         ops.layernorm_bwd(dx, sv["pe_pre"], d_pe, self.f32(pe + "norm.weight"), sv["pe_mean"], sv["pe_rstd"], B * HW, C, C, C, C,
@@ -433,21 +579,28 @@ class TrunkStep:
                           dgamma=self.gl(ten + "1.weight"), dbeta=self.gl(ten + "1.bias"), **self.lnk(), dy_map=rowmap(T, N, HW))
         if i == 0:
             K = m.in_chans * m.patch_size ** 2
-            ops.gemm_tn(d_pe, sv["P1"], self.g(pe + "proj.weight").view(C, K), B * HW, C, K, C, K, K, colsum=self.g(pe + "proj.bias"))
+            if on["patch"]:
+                ops.gemm_tn(d_pe, sv["P1"], self.g(pe + "proj.weight").view(C, K), B * HW, C, K, C, K, K, colsum=self.g(pe + "proj.bias"))
             # (round 6: the text-embedding weight gradients leave as partial tiles too -- 64 x 768 over 32768 rows: 64 splits' atomics on 1536 cache lines were 56 us)
-            ops.gemm_tn(d_te, self.emb, self.g(ten + "0.weight"), B * T, C, m.hidden, C, m.hidden, m.hidden, colsum=self.g(ten + "0.bias"),
-                        **self.tn())
-            d_emb = _empty((B * T, m.hidden), dt, dev)
-            ops.gemm_nt(d_te, self.wT(ten + "0.weight"), d_emb, B * T, m.hidden, C, C, C, m.hidden)
-            self._bert_backward(d_emb)
+            if on["text"]:
+                ops.gemm_tn(d_te, self.emb, self.g(ten + "0.weight"), B * T, C, m.hidden, C, m.hidden, m.hidden, colsum=self.g(ten + "0.bias"),
+                            **self.tn())
+            if u.dgrad:                            # (= some tensor of the BERT embedding block is trainable: it is the only unit below)
+                d_emb = _empty((B * T, m.hidden), dt, dev)
+                ops.gemm_nt(d_te, self.wT(ten + "0.weight"), d_emb, B * T, m.hidden, C, C, C, m.hidden)
+                self._bert_backward(d_emb)
             return None
         Cp, Np, HWp = m.dims[i - 1], self.saved[i - 1]["N"], self.saved[i - 1]["HW"]
         xp = sv["x_in_prev"]
         pm = sv["pm_in"]
         # conv weight gradient: computed in the gather's [out][kh][kw][cin] order, accumulated at its [out][cin][kh][kw] place
-        conv_wgrad(self.S, pe + "proj.weight", d_pe, xp, B * HW, C, 4 * Cp, C, Cp, pm, 4, Cp, colsum=self.g(pe + "proj.bias"))
-        ops.gemm_tn(d_te, xp, self.g(ten + "0.weight"), B * T, C, Cp, C, Cp, Cp, b_map=rowmap(T, Np, HWp), colsum=self.g(ten + "0.bias"),
-                    **self.tn())
+        if on["patch"]:
+            conv_wgrad(self.S, pe + "proj.weight", d_pe, xp, B * HW, C, 4 * Cp, C, Cp, pm, 4, Cp, colsum=self.g(pe + "proj.bias"))
+        if on["text"]:
+            ops.gemm_tn(d_te, xp, self.g(ten + "0.weight"), B * T, C, Cp, C, Cp, Cp, b_map=rowmap(T, Np, HWp), colsum=self.g(ten + "0.bias"),
+                        **self.tn())
+        if not u.dgrad:
+            return None
         dxp = into.view(B, Np, Cp) if into is not None else _empty((B, Np, Cp), dt, dev)
         ops.gemm_nt(d_pe, self.wKT(pe + "proj.weight"), dxp, B * HW, 4 * Cp, C, C, C, Cp, c_map=pm, R=into)          # image rows (each once)
         ops.gemm_nt(d_te, self.wT(ten + "0.weight"), dxp, B * T, Cp, C, C, C, Cp, c_map=rowmap(T, Np, HWp), R=into)   # text rows
@@ -483,15 +636,23 @@ class TrunkStep:
         M = B * N
         p = Names.blk(i, j)
         f32 = torch.float32
+        u = self.unit(f"block{i+1}.{j}")
+        on = u.launches
+        # the plan's cut with only MLP weights / biases trainable in this block: their gradients need d(block output) alone -- the pass ends here
+        mlp_only = not u.dgrad and u.only("fc1", "fc2")
         # ---- MLP branch: x_out = x_mid + s2 * (fc2(gelu(fc1(LN2(x_mid)))))
         dxn2 = _empty((M, C), dt, dev)
         # the DropPath-scaled copy of d(x_mid), the gradient of the attention branch x_mid = x + s1 * proj(attn(LN1(x))), comes out of norm2's backward
         fuse = bs["s1"] is not None
         if bs["fused_mlp"]:
             w1, w2t = self.w(p + "mlp.fc1.weight"), self.wT(p + "mlp.fc2.weight")
-            ops.mlp_bwd_dw(bs["xn2"], dx, w1, w2t, self.f32(p + "mlp.fc1.bias"), self.g(p + "mlp.fc1.weight"), self.g(p + "mlp.fc1.bias"),
-                           self.g(p + "mlp.fc2.weight"), self.g(p + "mlp.fc2.bias"), M, C, hid, row_scale=bs["s2"], rows_per_scale=N,
-                           **self.tn())
+            if on["fc1"] or on["fc2"]:
+                ops.mlp_bwd_dw(bs["xn2"], dx, w1, w2t, self.f32(p + "mlp.fc1.bias"), self.g(p + "mlp.fc1.weight"), self.g(p + "mlp.fc1.bias"),
+                               self.g(p + "mlp.fc2.weight"), self.g(p + "mlp.fc2.bias"), M, C, hid, row_scale=bs["s2"], rows_per_scale=N,
+                               **self.tn())
+            if mlp_only:
+                bs.clear()
+                return dx
             # ... and norm2's backward rides on the dx kernel's epilogue (the row of d(LN output) is in registers there): dx is
             # updated in place, the DropPath-scaled copy for the attention branch comes out of the same pass, no dxn2 round trip
             dy1 = _empty((M, C), dx.dtype, dev) if fuse else dx
@@ -505,11 +666,19 @@ class TrunkStep:
             self._dy2_pre = None
             if dy2 is None:
                 dy2 = self._scaled(dx, bs["s2"], N)
-            ops.gemm_tn(dy2, bs["gact"], self.g(p + "mlp.fc2.weight"), M, C, hid, C, hid, hid, colsum=self.g(p + "mlp.fc2.bias"), **self.tn())
+            if on["fc2"]:
+                ops.gemm_tn(dy2, bs["gact"], self.g(p + "mlp.fc2.weight"), M, C, hid, C, hid, hid, colsum=self.g(p + "mlp.fc2.bias"), **self.tn())
+            if mlp_only and not on["fc1"]:
+                bs.clear()
+                return dx
             dh = _empty((M, hid), dt, dev)
             ops.gemm_nt(dy2, self.wT(p + "mlp.fc2.weight"), dh, M, hid, C, C, C, hid, act=2, H=bs["hpre"])
             bs["gact"] = bs["hpre"] = None
-            ops.gemm_tn(dh, bs["xn2"], self.g(p + "mlp.fc1.weight"), M, hid, C, hid, C, C, colsum=self.g(p + "mlp.fc1.bias"), **self.tn())
+            if on["fc1"]:
+                ops.gemm_tn(dh, bs["xn2"], self.g(p + "mlp.fc1.weight"), M, hid, C, hid, C, C, colsum=self.g(p + "mlp.fc1.bias"), **self.tn())
+            if mlp_only:
+                bs.clear()
+                return dx
             ops.gemm_nt(dh, self.wT(p + "mlp.fc1.weight"), dxn2, M, C, hid, hid, hid, C)
             del dh
             # dx += LN2 backward = d(x_mid); the same kernel writes its DropPath-scaled copy
@@ -520,12 +689,14 @@ class TrunkStep:
         # stages 1-2 (C = 64 / 128, HBM-bound): the weight gradient and the input gradient of a C x C Linear come out of ONE pass over dY
         lin_fuse = dt == torch.bfloat16 and C in (64, 128)
         dao = dxn2          # reuse
-        if lin_fuse:
+        # (a frozen weight + bias: no weight gradient, and the fused launch gives way to the plain input-gradient GEMM of stages 3-4)
+        if lin_fuse and on["proj"]:
             ops.gemm_tn(dy1, bs["ao"], self.g(p + "attn.proj.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.proj.bias"),
                         dgrad=(self.wT(p + "attn.proj.weight"), dao.view(M, C)))
         else:
             # (stages 3-4: 9-16 output tiles x 32-56 m-splits -- reduced through bf16 partial tiles + a fold instead of atomics: mvlt_gemm_tn_args.partials)
-            ops.gemm_tn(dy1, bs["ao"], self.g(p + "attn.proj.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.proj.bias"), **self.tn())
+            if on["proj"]:
+                ops.gemm_tn(dy1, bs["ao"], self.g(p + "attn.proj.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.proj.bias"), **self.tn())
             ops.gemm_nt(dy1, self.wT(p + "attn.proj.weight"), dao, M, C, C, C, C, C)
         Mk = bs["Mk"]
         dq = _empty((B, N, C), dt, dev)
@@ -541,31 +712,36 @@ class TrunkStep:
             del dkv32
         # q projection
         dxn1 = dao          # reuse again: d(LN1 output), every row written by the q dgrad
-        if lin_fuse:
+        if lin_fuse and on["q"]:
             ops.gemm_tn(dq, bs["xn1"], self.g(p + "attn.q.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.q.bias"),
                         dgrad=(self.wT(p + "attn.q.weight"), dxn1.view(M, C)))
         else:
-            ops.gemm_tn(dq, bs["xn1"], self.g(p + "attn.q.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.q.bias"), **self.tn())
+            if on["q"]:
+                ops.gemm_tn(dq, bs["xn1"], self.g(p + "attn.q.weight"), M, C, C, C, C, C, colsum=self.g(p + "attn.q.bias"), **self.tn())
             ops.gemm_nt(dq, self.wT(p + "attn.q.weight"), dxn1, M, C, C, C, C, C)
         gkvw, gkvb = self.g(p + "attn.kv.weight"), self.g(p + "attn.kv.bias")
         wkvT = self.wT(p + "attn.kv.weight")
         if r > 1:
             HWr, pm = bs["HWr"], bs["pm"]
             # text keys come straight from LN1(x)[text rows]
-            ops.gemm_tn(dkv, bs["xn1"], gkvw, B * T, 2 * C, C, 2 * C, C, C, a_map=rowmap(T, Mk, HWr), b_map=rowmap(T, N, HW), colsum=gkvb, **self.tn())
+            if on["kv"]:
+                ops.gemm_tn(dkv, bs["xn1"], gkvw, B * T, 2 * C, C, 2 * C, C, C, a_map=rowmap(T, Mk, HWr), b_map=rowmap(T, N, HW), colsum=gkvb, **self.tn())
             ops.gemm_nt(dkv, wkvT, dxn1, B * T, C, 2 * C, 2 * C, 2 * C, C, a_map=rowmap(T, Mk, HWr), c_map=rowmap(T, N, HW), R=dxn1)
             # image keys: kv <- LN(sr conv(LN1(x)[image rows]))
-            ops.gemm_tn(dkv, bs["kvin"], gkvw, B * HWr, 2 * C, C, 2 * C, C, C, a_map=rowmap(HWr, Mk, 0), colsum=gkvb, **self.tn())
+            if on["kv"]:
+                ops.gemm_tn(dkv, bs["kvin"], gkvw, B * HWr, 2 * C, C, 2 * C, C, C, a_map=rowmap(HWr, Mk, 0), colsum=gkvb, **self.tn())
             dkvin = _empty((B * HWr, C), dt, dev)
             ops.gemm_nt(dkv, wkvT, dkvin, B * HWr, C, 2 * C, 2 * C, 2 * C, C, a_map=rowmap(HWr, Mk, 0))
             dsr = _empty((B * HWr, C), dt, dev)
             ops.layernorm_bwd(dkvin, bs["sr_pre"], dsr, self.f32(p + "attn.norm.weight"), bs["msr"], bs["rsr"], B * HWr, C, C, C, C,
                               dgamma=self.gl(p + "attn.norm.weight"), dbeta=self.gl(p + "attn.norm.bias"), **self.lnk())
             K = r * r * C
-            conv_wgrad(self.S, p + "attn.sr.weight", dsr, bs["xn1"], B * HWr, C, K, C, C, pm, r * r, C, colsum=self.g(p + "attn.sr.bias"))
+            if on["sr"]:
+                conv_wgrad(self.S, p + "attn.sr.weight", dsr, bs["xn1"], B * HWr, C, K, C, C, pm, r * r, C, colsum=self.g(p + "attn.sr.bias"))
             ops.gemm_nt(dsr, self.wKT(p + "attn.sr.weight"), dxn1, B * HWr, K, C, C, C, C, c_map=pm, R=dxn1)
         else:
-            ops.gemm_tn(dkv, bs["xn1"], gkvw, M, 2 * C, C, 2 * C, C, C, colsum=gkvb, **self.tn())
+            if on["kv"]:
+                ops.gemm_tn(dkv, bs["xn1"], gkvw, M, 2 * C, C, 2 * C, C, C, colsum=gkvb, **self.tn())
             ops.gemm_nt(dkv, wkvT, dxn1, M, C, 2 * C, 2 * C, 2 * C, C, R=dxn1)
         # the block below (processed next) scales this gradient by its own MLP-branch DropPath factor first thing when its MLP is not the
         # fused kernel (stages 3-4): norm1's backward writes that scaled copy in the same pass
@@ -588,7 +764,7 @@ class _TrunkFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, images, ids, need_grad, *params):
-        step = TrunkStep(model, images, ids, need_grad)
+        step = TrunkStep(model, images, ids, need_grad, getattr(model, "_plan", None))
         outs = step.forward()
         ctx.step = step
         ctx.pool_token, model._pool_token = model._pool_token, None      # this node's life = the time the step's pooled scratch is owned
@@ -604,16 +780,42 @@ class _TrunkFn(torch.autograd.Function):
         step.backward([None, d2, d3, d4])
         ctx.step = None
         ctx.pool_token = None
-        grads = []
-        for k, (name, p) in enumerate(S.fn_params):
-            gv = S.grad(name)
-            if not ctx.needs_input_grad[4 + k]:
-                grads.append(None)
-            elif p.grad is not None and p.grad.data_ptr() == gv.data_ptr():
-                grads.append(None)          # .grad already aliases the flat buffer (accumulation without zero_grad)
-            else:
-                grads.append(gv)
-        return (None, None, None, None, *grads)
+        return (None, None, None, None, *_grad_slices(S, ctx, 4))
+
+
+def _grad_slices(S, ctx, first):
+    """what a parameter-carrying node returns to autograd: the finished slices of the flat gradient buffer (see _TrunkFn)"""
+    grads = []
+    for k, (name, p) in enumerate(S.fn_params):
+        gv = S.grad(name)
+        if not ctx.needs_input_grad[first + k]:
+            grads.append(None)          # frozen: .grad stays None
+        elif p.grad is not None and p.grad.data_ptr() == gv.data_ptr():
+            grads.append(None)          # .grad already aliases the flat buffer (accumulation without zero_grad)
+        else:
+            grads.append(gv)
+    return grads
+
+
+class _FrozenTrunkFn(torch.autograd.Function):
+    """Stands where _TrunkFn stands when no trunk unit has a trainable parameter (a linear probe: only heads train).  The trunk has then run outside
+    autograd, exactly as under torch.no_grad() -- nothing saved, no trunk node; this node only ties the stage outputs the heads read to the parameters,
+    so that the head nodes get their backward and, after all of them, the trainable parameters get their slices of the flat gradient buffer."""
+
+    @staticmethod
+    def forward(ctx, model, x2, x3, x4, *params):
+        ctx.S = model.store
+        ctx.pool_token, model._pool_token = model._pool_token, None
+        ctx.set_materialize_grads(False)
+        return x2.detach(), x3.detach(), x4.detach()
+
+    @staticmethod
+    def backward(ctx, d2, d3, d4):
+        S = ctx.S
+        S.queue_finalize()
+        ctx.pool_token = None
+        S.fold_copies()
+        return (None, None, None, None, *_grad_slices(S, ctx, 4))
 
 
 # =============================================================================================== heads
@@ -646,15 +848,22 @@ def _embed_ln_fwd(model, prefix, A, a_map, rows, lda):
     return y, (pre, mean, rstd)
 
 
-def _embed_ln_bwd(model, prefix, dy, saved, A, a_map, rows, lda, dA, c_map, accumulate):
+def _unit(plan, name):
+    return plan.by[name] if plan is not None else _EVERY
+
+
+def _embed_ln_bwd(model, prefix, dy, saved, A, a_map, rows, lda, dA, c_map, accumulate, unit=_EVERY):
+    """dA None: the input gradient is not needed (nothing in the trunk is trainable)"""
     S, dt, dev = model.store, model.compute_dtype, dy.device
     Hd, Cin = model.hidden, model.dims[3]
     pre, mean, rstd = saved
     dpre = _empty((rows, Hd), dt, dev)
     ops.layernorm_bwd(dy, pre, dpre, S.master(prefix + ".1.weight"), mean, rstd, rows, Hd, Hd, Hd, Hd,
                       dgamma=S.grad(prefix + ".1.weight"), dbeta=S.grad(prefix + ".1.bias"))
-    ops.gemm_tn(dpre, A, S.grad(prefix + ".0.weight"), rows, Hd, Cin, Hd, lda, Cin, b_map=a_map, colsum=S.grad(prefix + ".0.bias"))
-    ops.gemm_nt(dpre, S.extra[prefix + ".0.weight::T"], dA, rows, Cin, Hd, Hd, Hd, Cin, c_map=c_map, R=dA if accumulate else None)
+    if unit.launches["embed"]:
+        ops.gemm_tn(dpre, A, S.grad(prefix + ".0.weight"), rows, Hd, Cin, Hd, lda, Cin, b_map=a_map, colsum=S.grad(prefix + ".0.bias"))
+    if dA is not None:
+        ops.gemm_nt(dpre, S.extra[prefix + ".0.weight::T"], dA, rows, Cin, Hd, Hd, Hd, Cin, c_map=c_map, R=dA if accumulate else None)
 
 
 class _ClsHeadFn(torch.autograd.Function):
@@ -677,6 +886,7 @@ class _ClsHeadFn(torch.autograd.Function):
         logits = _empty((B, n_out), torch.float32, dev)
         ops.gemm_nt(e, S.comp(name + "_head.linear.weight"), logits, B, n_out, model.hidden, model.hidden, model.hidden, n_out, bias=bias)
         ctx.pack = (model, name, HW, x4, e, saved, a_map, sink)
+        ctx.unit = _unit(getattr(model, "_plan", None), name + "_head")
         return logits.view(B, 1, n_out)
 
     @staticmethod
@@ -684,6 +894,7 @@ class _ClsHeadFn(torch.autograd.Function):
         model, name, HW, x4, e, saved, a_map, sink = ctx.pack
         S, dt, dev = model.store, model.compute_dtype, x4.device
         S.queue_finalize()
+        u = ctx.unit
         B, N, C = x4.shape
         Hd = model.hidden
         n_out = dlogits.shape[-1]
@@ -698,13 +909,14 @@ class _ClsHeadFn(torch.autograd.Function):
             db = dlogits.reshape(B, n_out).float().sum(0)
             S.grad(name + "_head.linear.bias").add_(db)
             S.grad(name + "_head.linear_bias").add_(db)
-        ops.gemm_tn(dl, e, S.grad(name + "_head.linear.weight"), B, n_out, Hd, n_pad, Hd, Hd)
+        if u.launches["linear"]:
+            ops.gemm_tn(dl, e, S.grad(name + "_head.linear.weight"), B, n_out, Hd, n_pad, Hd, Hd)
         de = _empty((B, Hd), dt, dev)
         wT = S.extra[name + "_head.linear.weight::T"]          # [768, n_pad]
         ops.gemm_nt(dl, wT, de, B, Hd, n_pad, n_pad, wT.shape[1], Hd)
-        dx4, ret = (sink or _GradSink(S)).take(x4.shape, dt, dev)
-        _embed_ln_bwd(model, name + "_head_embed", de, saved, x4, a_map, B, C, dx4, a_map, True)
-        ctx.pack = None
+        dx4, ret = (sink or _GradSink(S)).take(x4.shape, dt, dev) if u.dgrad else (None, None)
+        _embed_ln_bwd(model, name + "_head_embed", de, saved, x4, a_map, B, C, dx4, a_map, True, u)
+        ctx.pack = ctx.unit = None
         S.announce_prefix(name + "_head_embed.", name + "_head.")
         return ret, None, None, None, None
 
@@ -723,7 +935,7 @@ def _mlm_transform_fwd(model, rows_in, R):
     return t, (hp, ga, mean, rstd)
 
 
-def _mlm_transform_bwd(model, dt_, saved, rows_in, R):
+def _mlm_transform_bwd(model, dt_, saved, rows_in, R, unit=_EVERY):
     S, dt, dev = model.store, model.compute_dtype, dt_.device
     Hd = model.hidden
     hp, ga, mean, rstd = saved
@@ -731,7 +943,8 @@ def _mlm_transform_bwd(model, dt_, saved, rows_in, R):
     ops.layernorm_bwd(dt_, ga, dga, S.master("mlm_head.transform.LayerNorm.weight"), mean, rstd, R, Hd, Hd, Hd, Hd,
                       dgamma=S.grad("mlm_head.transform.LayerNorm.weight"), dbeta=S.grad("mlm_head.transform.LayerNorm.bias"))
     dhp = ops.gelu_bwd(dga, hp, torch.empty_like(dga))             # d(pre-activation) = dga * gelu'(hp)
-    ops.gemm_tn(dhp, rows_in, S.grad("mlm_head.transform.dense.weight"), R, Hd, Hd, Hd, Hd, Hd, colsum=S.grad("mlm_head.transform.dense.bias"))
+    if unit.launches["dense"]:
+        ops.gemm_tn(dhp, rows_in, S.grad("mlm_head.transform.dense.weight"), R, Hd, Hd, Hd, Hd, Hd, colsum=S.grad("mlm_head.transform.dense.bias"))
     din = _empty((R, Hd), dt, dev)
     ops.gemm_nt(dhp, S.extra["mlm_head.transform.dense.weight::T"], din, R, Hd, Hd, Hd, Hd, Hd)
     return din
@@ -753,6 +966,7 @@ class _MLMFullFn(torch.autograd.Function):
         ops.gemm_nt(t, S.comp("text_embeddings.word_embeddings.weight"), buf, R, VOCAB, model.hidden, model.hidden, model.hidden, VOCAB_LD,
                     bias=S.master("mlm_head.bias"))
         ctx.pack = (model, HW, x4, e, sv_e, t, sv_t, a_map, sink)
+        ctx.unit = _unit(getattr(model, "_plan", None), "mlm_head")
         return buf.view(B, T, VOCAB_LD)[:, :, :VOCAB]
 
     @staticmethod
@@ -765,22 +979,30 @@ class _MLMFullFn(torch.autograd.Function):
         R = B * T
         dl = torch.zeros(R, VOCAB_LD, device=dev, dtype=dt)
         dl[:, :VOCAB] = dlogits.reshape(R, VOCAB).to(dt)
-        dx4, ret = (sink or _GradSink(S)).take(x4.shape, dt, dev)
-        _mlm_decoder_bwd(model, dl, t, sv_t, e, sv_e, x4, a_map, R, C, dx4, accumulate=True)
-        ctx.pack = None
+        u = ctx.unit
+        dx4, ret = (sink or _GradSink(S)).take(x4.shape, dt, dev) if u.dgrad else (None, None)
+        _mlm_decoder_bwd(model, dl, t, sv_t, e, sv_e, x4, a_map, R, C, dx4, accumulate=True, unit=u)
+        ctx.pack = ctx.unit = None
         return ret, None, None, None
 
 
-def _mlm_decoder_bwd(model, dl, t, sv_t, e, sv_e, A, a_map, R, lda, dA, c_map=None, accumulate=False):
-    """shared tail of both MLM paths: dl (R, VOCAB_LD) in the compute dtype -> every MLM-head gradient + dA rows."""
+def _mlm_decoder_bwd(model, dl, t, sv_t, e, sv_e, A, a_map, R, lda, dA, c_map=None, accumulate=False, unit=_EVERY):
+    """shared tail of both MLM paths: dl (R, VOCAB_LD) in the compute dtype -> every MLM-head gradient + dA rows (dA None: not needed)."""
     S, dt, dev = model.store, model.compute_dtype, dl.device
     Hd = model.hidden
-    wname = "text_embeddings.word_embeddings.weight"
-    # the first writer of the word table's gradient in a pass (bert_embed_bwd adds its lookup rows at the very end): when begin_backward zeroed the whole buffer for THIS
-    # pass the 23 M outputs are stored, not added by atomics (mvlt_gemm_tn_args.c_overwrite; a pass that accumulates onto earlier gradients keeps the atomics)
-    ops.gemm_tn(dl, t, S.grad(wname), R, VOCAB, Hd, VOCAB_LD, Hd, Hd, colsum=S.grad("mlm_head.bias"),
-                overwrite=dt == torch.bfloat16 and S.all_zeroed_this_pass and wname not in S.touched_this_pass)
-    S.touched_this_pass.add(wname)
+    wname = WORD_TABLE
+    if unit.launches["table"]:
+        # the first writer of the word table's gradient in a pass (bert_embed_bwd adds its lookup rows at the very end): when begin_backward zeroed the whole buffer for THIS
+        # pass the 23 M outputs are stored, not added by atomics (mvlt_gemm_tn_args.c_overwrite; a pass that accumulates onto earlier gradients keeps the atomics)
+        ops.gemm_tn(dl, t, S.grad(wname), R, VOCAB, Hd, VOCAB_LD, Hd, Hd, colsum=S.grad("mlm_head.bias"),
+                    overwrite=dt == torch.bfloat16 and S.all_zeroed_this_pass and wname not in S.touched_this_pass)
+        S.touched_this_pass.add(wname)
+    elif unit.launches["bias"]:
+        # frozen table: its 23 M-element weight gradient is not formed.  mlm_head.bias' gradient was that launch's column sum: now the plain sum of dl
+        # over its R rows (mvlt_batch_sum wants 8-element columns: the padded width, whose last columns hold zeros)
+        db = _empty((1, VOCAB_LD), torch.float32, dev)
+        ops.batch_sum(dl, db, R, 1, VOCAB_LD, 1, VOCAB_LD)
+        S.grad("mlm_head.bias").add_(db[0, :VOCAB])
     wT = S.extra[wname + "::T"]                                   # [768, VOCAB_LD], zero padded
     if dt == torch.bfloat16:
         # few output tiles (R x 768), K = 30528: cut K over 4 workgroups per tile, partial sums meet in an fp32 buffer
@@ -790,8 +1012,8 @@ def _mlm_decoder_bwd(model, dl, t, sv_t, e, sv_e, A, a_map, R, lda, dA, c_map=No
     else:
         dtr = _empty((R, Hd), dt, dev)
         ops.gemm_nt(dl, wT, dtr, R, Hd, VOCAB_LD, VOCAB_LD, VOCAB_LD, Hd)
-    de = _mlm_transform_bwd(model, dtr, sv_t, e, R)
-    _embed_ln_bwd(model, "mlm_head_embed", de, sv_e, A, a_map, R, lda, dA, c_map if c_map is not None else a_map, accumulate)
+    de = _mlm_transform_bwd(model, dtr, sv_t, e, R, unit)
+    _embed_ln_bwd(model, "mlm_head_embed", de, sv_e, A, a_map, R, lda, dA, c_map if c_map is not None else a_map, accumulate, unit)
     # final now: the head's own parameters.  The tied decoder weight is the word-embedding table, which bert_embed_bwd still adds
     # to at the very end of the pass: it travels with the leftovers.
     S.announce_prefix("mlm_head_embed.", "mlm_head.")
@@ -819,6 +1041,7 @@ class _MLMFusedFn(torch.autograd.Function):
         acc = pool_zeros((2,), torch.float32, dev)                     # [loss_sum, count]; pooled scratch lives until the next forward
         ops.cross_entropy_fwd(logits, labels_sel, lse, acc[0:1], acc[1:2], R, VOCAB, VOCAB_LD)
         ctx.pack = (model, HW, x4.shape, rows, e, sv_e, t, sv_t, logits, lse, acc, positions, labels_sel, tmap, sink)
+        ctx.unit = _unit(getattr(model, "_plan", None), "mlm_head")
         return acc[0] / acc[1]          # mean over selected rows (NaN when none, like torch)
 
     @staticmethod
@@ -831,11 +1054,14 @@ class _MLMFusedFn(torch.autograd.Function):
         dl = _empty((R, VOCAB_LD), dt, dev)
         gs = gloss.reshape(1).float().contiguous()
         ops.cross_entropy_bwd(logits, labels_sel, lse, gs, acc[1:2], dl, R, VOCAB, VOCAB_LD, VOCAB_LD)
-        drows = _empty((R, C), dt, dev)
-        _mlm_decoder_bwd(model, dl, t, sv_t, e, sv_e, rows, None, R, C, drows, c_map=None)
-        dx4, ret = (sink or _GradSink(S)).take(xshape, dt, dev)
-        ops.scatter_rows(drows, positions, dx4, R, C, C, dst_map=tmap, accumulate=True)
-        ctx.pack = None
+        u = ctx.unit
+        drows = _empty((R, C), dt, dev) if u.dgrad else None
+        _mlm_decoder_bwd(model, dl, t, sv_t, e, sv_e, rows, None, R, C, drows, c_map=None, unit=u)
+        ret = None
+        if u.dgrad:
+            dx4, ret = (sink or _GradSink(S)).take(xshape, dt, dev)
+            ops.scatter_rows(drows, positions, dx4, R, C, C, dst_map=tmap, accumulate=True)
+        ctx.pack = ctx.unit = None
         return ret, None, None, None, None, None
 
 
@@ -882,7 +1108,7 @@ def run_forward(model, images, ids, mlm_labels=None, mlm_positions=None, mlm_cou
         ops.masked_select(flat, idx, cnt)
         sel = (idx, mlm_count if mlm_count is not None else _HostCount(cnt))
     S.refresh(model._transposed, model._conv_perm, model._conv3)
-    x1, x2, x3, x4 = _TrunkFn.apply(model, images, ids, grad_on, *[p for _, p in S.fn_params])
+    x1, x2, x3, x4 = _trunk(model, images, ids, grad_on, heads=True)
     sink = _GradSink(S) if grad_on else None            # the heads' common gradient buffer for x4
     B = images.shape[0]
     grids = stage_grids(model, images.shape[2], images.shape[3])
@@ -927,11 +1153,27 @@ def _begin_pass(model, dev):
     """common head of every forward entry: flat store on the device, one fill for all of this step's zero-initialised scratch"""
     S = model.store
     S.ensure(dev)
-    grad_on = torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters())
+    # requires_grad is read HERE, once per forward: the plan of this pass (what its backward runs, what its forward keeps)
+    model._plan = plan = _plan_for(model) if torch.is_grad_enabled() else None
+    grad_on = plan is not None and plan.cut is not None
     model._pool_token = ZeroPool.of(dev).reset(grad_on)
     if grad_on:
         S.new_pass()                                              # a backward that raised must not poison this pass (FlatStore.new_pass)
     return grad_on
+
+
+def _trunk(model, images, ids, grad_on, heads):
+    """The four stage outputs.  With a trainable parameter in the trunk: one autograd node (_TrunkFn).  With none the trunk runs as it does under
+    torch.no_grad() -- nothing kept, no node; `heads`: trainable heads follow, which reach their backward through _FrozenTrunkFn."""
+    S = model.store
+    params = [p for _, p in S.fn_params]
+    if not grad_on or model._plan.trunk_save:
+        return _TrunkFn.apply(model, images, ids, grad_on, *params)
+    x1, x2, x3, x4 = TrunkStep(model, images, ids, False).forward()
+    if not heads:
+        model._pool_token = None
+        return x1, x2, x3, x4
+    return (x1, *_FrozenTrunkFn.apply(model, x2, x3, x4, *params))
 
 
 def run_trunk(model, images, ids):
@@ -940,4 +1182,4 @@ def run_trunk(model, images, ids):
     S = model.store
     grad_on = _begin_pass(model, images.device)
     S.refresh(model._transposed, model._conv_perm, model._conv3)
-    return _TrunkFn.apply(model, images, ids, grad_on, *[p for _, p in S.fn_params])
+    return _trunk(model, images, ids, grad_on, heads=False)
