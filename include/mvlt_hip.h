@@ -204,7 +204,8 @@ int mvlt_batch_sum(const void* in, float* out, int B, int R, int C, long batch_s
  * libs/pvlt.py:113-117 applies none).  Q: (B,N,ldq) with head h at columns [64h,64h+64); K,V: (B,M,ldkv)
  * rows, head h at columns k_off+64h / v_off+64h of the kv buffer; O like Q.  lse[B,H,N] fp32 saved for bwd.
  * lse = ref * scale + log(sum of exp((s - ref) * scale)) where ref is a row maximum of the scores (bf16, M <= 192: the maximum over the
- * first half of the keys unless the second half tops it by 2^24 -- the value of lse does not depend on which). */
+ * first half of the keys unless the second half tops it by 2^24 -- the value of lse does not depend on which; past 32 keys that kernel sums the
+ * exponentials rounded to bf16, as its P V product sees them). */
 typedef struct mvlt_attn_args {
   const void* Q; const void* KV; void* O; float* lse;
   int B, H, N, M;

@@ -425,12 +425,23 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_fwd2_kernel(mvl
     return fmaxf(m, __shfl_xor(m, 32));
   };
   float mneg, sum, mref;
+  // the denominator sums the numerators AS THE P V MFMAs SEE THEM, rounded to bf16 (one v_dot2 per pair in place of two adds; the pairs are those
+  // mmaPV converts): the reference maximum is block 0's, so a row decided by ONE key of block 1 has a numerator like 2^23.08 that bf16 does not
+  // hold, and with the unrounded sum its O came out as V x bf16(e) / e -- up to 2^-8 off, which the backward's D = rowsum(dO x O) turned into a dS
+  // where there is none (tests/test_attention_edges_gpu.py::test_backward_of_the_forwards_own_output)
+  // (In the `far` branch below block 0's remaining numerators are scaled by alpha < 2^-24 AFTER their rounded values went into the sum, so the MFMAs see
+  // bf16(alpha e) against the sum's alpha bf16(e): terms 2^-24 of the row's largest, below the sum's own rounding.)
+  // (up to 32 keys there is no block 1: the reference IS the row maximum, the deciding numerator is exactly 1, and the plain sum stays)
+  const bf16x2 one2 = {(bf16)1.0f, (bf16)1.0f};
   auto expo = [&](f32x16& acc) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[r], sl2, mneg));
-      acc[r] = e;
-      sum += e;
+    for (int r = 0; r < 16; r += 2) {
+      const float e0 = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[r], sl2, mneg));
+      const float e1 = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[r + 1], sl2, mneg));
+      acc[r] = e0;
+      acc[r + 1] = e1;
+      if constexpr (BT1 > 0) sum = __builtin_amdgcn_fdot2_f32_bf16(__builtin_convertvector(f32x2{e0, e1}, bf16x2), one2, sum, false);
+      else sum += e0, sum += e1;
     }
   };
   using P0 = std::integral_constant<int, 0>;
