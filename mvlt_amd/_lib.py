@@ -37,7 +37,7 @@ class GemmNTArgs(C.Structure):
                 ("bias", c_void_p), ("act", c_int), ("H", c_void_p),
                 ("row_scale", c_void_p), ("rows_per_scale", c_int), ("R", c_void_p),
                 ("col_sum", c_void_p), ("col_sumsq", c_void_p), ("col_copies", c_int), ("split_k", c_int),
-                ("post_y", c_void_p), ("post_ld", c_int), ("post_gamma", c_void_p), ("post_beta", c_void_p), ("post_eps", C.c_float),
+                ("post_y", c_void_p), ("post_ld", c_int), ("post_gamma", c_void_p), ("post_beta", c_void_p), ("post_eps", c_float),
                 ("post_mean", c_void_p), ("post_rstd", c_void_p), ("r_fp32", c_int)]
 
 
@@ -72,7 +72,7 @@ class LayerNormBwdArgs(C.Structure):
                 ("dy_map", RowMap), ("x_map", RowMap), ("dx_map", RowMap),
                 ("dx_accumulate", c_int), ("dtype", c_int), ("x_dtype", c_int), ("dx_dtype", c_int),
                 ("dx2", c_void_p), ("dx2_scale", c_void_p), ("dx2_rows_per_scale", c_int), ("lddx2", c_int),
-                ("dg_copies", c_int), ("dg_copy_stride", C.c_long)]
+                ("dg_copies", c_int), ("dg_copy_stride", c_long)]
 
 
 class AttnArgs(C.Structure):
@@ -104,29 +104,94 @@ class MlpArgs(C.Structure):
                 ("lnb_partials", c_void_p), ("partials", c_void_p), ("partials_bytes", c_long), ("defer_fold", c_int)]
 
 
-lib.mvlt_last_error.restype = C.c_char_p
-lib.mvlt_last_kernel.restype = C.c_char_p
-lib.mvlt_sizeof.argtypes = [C.c_char_p]
+# header name -> class of every argument struct: the import-time size check below and the header-against-binding test walk it
+STRUCTS = (("mvlt_rowmap", RowMap), ("mvlt_prep_desc", PrepDesc), ("mvlt_gemm_nt_args", GemmNTArgs), ("mvlt_gemm_tn_args", GemmTNArgs),
+           ("mvlt_layernorm_args", LayerNormArgs), ("mvlt_layernorm_bwd_args", LayerNormBwdArgs),
+           ("mvlt_attn_args", AttnArgs), ("mvlt_attn_bwd_args", AttnBwdArgs), ("mvlt_mlp_args", MlpArgs))
+
+# entry point -> (restype, argtypes), parameter by parameter as include/mvlt_hip.h declares them (tests/test_host_cpu.py compares the two).  Every pointer a
+# tensor goes into is c_void_p, so ptr() hands over plain ints; struct arguments are POINTER(class) and take C.byref(args).
+_vp, _i, _l, _f, _u64, _str = c_void_p, c_int, c_long, c_float, C.c_uint64, C.c_char_p
+_by_args = lambda cls: (_i, [C.POINTER(cls), _vp])          # int f(const <struct>* args, void* stream)
+PROTOTYPES = {
+    "mvlt_last_error": (_str, []),
+    "mvlt_abi_version": (_i, []),
+    "mvlt_last_kernel": (_str, []),
+    "mvlt_sizeof": (_i, [_str]),
+    "mvlt_gemm_nt": _by_args(GemmNTArgs),
+    "mvlt_gemm_tn": _by_args(GemmTNArgs),
+    "mvlt_tn_fold_flush": (_i, [_vp, _vp]),
+    "mvlt_tn_fold_discard": (_i, [_vp]),
+    "mvlt_layernorm_fwd": _by_args(LayerNormArgs),
+    "mvlt_layernorm_bwd": _by_args(LayerNormBwdArgs),
+    "mvlt_fold_copies": (_i, [_vp, _i, _l, _vp, _i, _i, _vp, _vp]),
+    "mvlt_batch_sum": (_i, [_vp, _vp, _i, _i, _i, _l, _i, _i, _vp, _i, _vp]),
+    "mvlt_sr_attention_fwd": _by_args(AttnArgs),
+    "mvlt_sr_attention_bwd": _by_args(AttnBwdArgs),
+    "mvlt_sr_attention_bwd_chunks": (_i, [_i] * 5),
+    "mvlt_sr_attention_fwd_streamed": _by_args(AttnArgs),
+    "mvlt_sr_attention_bwd_streamed": _by_args(AttnBwdArgs),
+    # csrc/elementwise.hip
+    "mvlt_bert_embed_fwd": (_i, [_vp] * 7 + [_f, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
+    "mvlt_bert_embed_bwd": (_i, [_vp] * 7 + [_f] + [_vp] * 7 + [_i, _i, _i, _i, _vp]),
+    "mvlt_patchify": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mvlt_masked_select": (_i, [_vp, _i, _l, _vp, _vp, _vp]),
+    "mvlt_resize_bilinear_tokens": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "mvlt_resize_bilinear_tokens_multi": (_i, [_vp] * 9 + [_i, _i, _vp]),
+    "mvlt_gelu_bwd": (_i, [_vp, _vp, _vp, _l, _i, _vp]),
+    "mvlt_loss_compose": (_i, [C.POINTER(c_void_p), C.POINTER(c_float), _vp, _vp, _vp]),
+    # csrc/batchprep.hip
+    "mvlt_grid_mask_flags": (_i, [_vp, _i, _i, _i, _i, _i, _u64, _u64, _vp]),
+    "mvlt_grid_mask_apply": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "mvlt_token_mask": (_i, [_vp, _vp, _vp, _i, _i, _u64, _u64, _i, _vp]),
+    "mvlt_keep_mask": (_i, [_vp, _l, _f, _u64, _u64, _vp]),
+    "mvlt_droppath_scales": (_i, [_vp, _vp, _i, _i, _u64, _u64, _vp]),
+    "mvlt_gather_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(RowMap), _i, _vp]),
+    "mvlt_scatter_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(RowMap), _i, _i, _vp]),
+    "mvlt_cross_entropy_fwd": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvlt_cross_entropy_bwd": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mvlt_smooth_l1_fwd": (_i, [_vp, _vp, _l, _vp, _vp]),
+    "mvlt_smooth_l1_bwd": (_i, [_vp, _vp, _l, _vp, _vp, _vp]),
+    "mvlt_adamw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp]),
+    "mvlt_grad_sumsq": (_i, [_vp, _l, _vp, _vp, _i, _vp]),
+    "mvlt_clip_coef": (_i, [_vp, _i, _f, _f, _vp, _vp]),
+    "mvlt_scale_by_dev": (_i, [_vp, _l, _vp, _vp]),
+    "mvlt_cast_bf16": (_i, [_vp, _vp, _l, _vp]),
+    "mvlt_row_scale": (_i, [_vp, _vp, _i, _l, _i, _vp, _i, _vp]),
+    "mvlt_head_grad_prep": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "mvlt_transpose_cast": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvlt_weight_prep": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp]),          # descs: a DEVICE table of PrepDesc, hence no POINTER(PrepDesc)
+    # csrc/mlp.hip
+    "mvlt_mlp_fwd": _by_args(MlpArgs),
+    "mvlt_mlp_bwd_dx": _by_args(MlpArgs),
+    "mvlt_mlp_bwd_dw": _by_args(MlpArgs),
+    "mvlt_add_column_sums": (_i, [_vp, _l, _i, _i, _vp, _i, _vp, _vp]),
+    # csrc/mim.hip
+    "mvlt_col_stats": (_i, [_vp, _i, _l, _i, _vp, _vp, _vp]),
+    "mvlt_bn_finalize": (_i, [_vp, _vp, _i, _l, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "mvlt_bn_norm": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _l, _i, _vp, _i, _i, _vp, _i, _i, _vp]),
+    "mvlt_bn_finalize_norm": (_i, [_vp, _i, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _vp, _i, _i, _vp, _i, _vp]),
+    "mvlt_bn_bwd_reduce": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _l, _i, _vp, _vp, _i, _vp]),
+    "mvlt_bn_bwd_apply": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _i, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    "mvlt_ew_mul": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _l, _i, _i, _vp, _i, _i, _vp]),
+    "mvlt_ew_mul3_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _l, _i, _i, _vp]),
+    "mvlt_upsample_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
+    "mvlt_upsample_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "mvlt_upsample_l1_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mvlt_upsample_l1_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
+}
+EXPORTS = list(PROTOTYPES)
+for _name, (_res, _args) in PROTOTYPES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
 ABI_VERSION = 8          # include/mvlt_hip.h MVLT_ABI_VERSION this binding was written against
 if lib.mvlt_abi_version() != ABI_VERSION:
     raise ImportError(f"ABI mismatch: {LIB_PATH} is version {lib.mvlt_abi_version()}, the binding is version {ABI_VERSION} (stale build? run python -m mvlt_amd.build)")
-for _name, _cls in (("mvlt_rowmap", RowMap), ("mvlt_prep_desc", PrepDesc), ("mvlt_gemm_nt_args", GemmNTArgs), ("mvlt_gemm_tn_args", GemmTNArgs),
-                    ("mvlt_layernorm_args", LayerNormArgs), ("mvlt_layernorm_bwd_args", LayerNormBwdArgs),
-                    ("mvlt_attn_args", AttnArgs), ("mvlt_attn_bwd_args", AttnBwdArgs), ("mvlt_mlp_args", MlpArgs)):
+for _name, _cls in STRUCTS:
     _n = lib.mvlt_sizeof(_name.encode())
     if _n != C.sizeof(_cls):
         raise ImportError(f"ABI mismatch for {_name}: library says {_n} bytes, binding has {C.sizeof(_cls)}")
-
-EXPORTS = ["mvlt_last_error", "mvlt_last_kernel", "mvlt_abi_version", "mvlt_sizeof", "mvlt_gemm_nt", "mvlt_gemm_tn",
-           "mvlt_layernorm_fwd", "mvlt_layernorm_bwd", "mvlt_fold_copies", "mvlt_batch_sum", "mvlt_sr_attention_fwd", "mvlt_sr_attention_bwd",
-           "mvlt_bert_embed_fwd", "mvlt_bert_embed_bwd", "mvlt_patchify", "mvlt_masked_select", "mvlt_gather_rows",
-           "mvlt_scatter_rows", "mvlt_cross_entropy_fwd", "mvlt_cross_entropy_bwd", "mvlt_adamw_step", "mvlt_smooth_l1_fwd", "mvlt_smooth_l1_bwd", "mvlt_cast_bf16",
-           "mvlt_transpose_cast", "mvlt_row_scale", "mvlt_head_grad_prep", "mvlt_weight_prep", "mvlt_col_stats", "mvlt_bn_finalize", "mvlt_bn_finalize_norm", "mvlt_bn_norm", "mvlt_bn_bwd_reduce", "mvlt_bn_bwd_apply", "mvlt_ew_mul3_bwd",
-           "mvlt_ew_mul", "mvlt_upsample_fwd", "mvlt_upsample_bwd", "mvlt_mlp_fwd", "mvlt_mlp_bwd_dx", "mvlt_mlp_bwd_dw",
-           "mvlt_grid_mask_flags", "mvlt_grid_mask_apply", "mvlt_token_mask", "mvlt_resize_bilinear_tokens", "mvlt_resize_bilinear_tokens_multi", "mvlt_gelu_bwd",
-           "mvlt_keep_mask", "mvlt_droppath_scales", "mvlt_loss_compose", "mvlt_add_column_sums",
-           "mvlt_upsample_l1_fwd", "mvlt_upsample_l1_bwd", "mvlt_tn_fold_flush", "mvlt_tn_fold_discard", "mvlt_sr_attention_bwd_chunks",
-           "mvlt_sr_attention_fwd_streamed", "mvlt_sr_attention_bwd_streamed", "mvlt_grad_sumsq", "mvlt_clip_coef", "mvlt_scale_by_dev"]
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 
@@ -158,15 +223,16 @@ _raw_stream, _cur_device = torch._C._cuda_getCurrentRawStream, torch._C._cuda_ge
 def stream_ptr():
     """torch's current stream of the current device as a hipStream_t (two C calls: `torch.cuda.current_stream().cuda_stream` walks ~10 Python frames and
     builds a Stream object -- 358 launches per step made that 2.5 ms of a 10 ms host step, tools/host_profile.py)"""
-    return c_void_p(_raw_stream(_cur_device()))
+    return _raw_stream(_cur_device())
 
 
 def ptr(t):
+    """the one way a tensor becomes an argument: its device address as a plain int (the c_void_p argtypes and struct fields convert it), None for None"""
     if t is None:
         return None
     if not t.is_cuda:
         raise MVLTError("mvlt_amd ops need CUDA/HIP tensors (no CPU fallback)")
-    return c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 def rowmap(rows_per_batch=0, batch_stride=0, offset=0):

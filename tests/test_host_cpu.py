@@ -14,17 +14,72 @@ from oracle import pvlt_oracle as O
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _header_abi(hdr):
+    """include/mvlt_hip.h without its comments -> ({function: (return type, [parameter types])}, {struct: [(field, type)]}); types as written, '*' attached"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", hdr, flags=re.S)
+    norm = lambda t: re.sub(r"\s*\*\s*", "* ", " ".join(t.split())).strip()
+    protos = {}
+    for ret, name, params in re.findall(r"\b(int|const\s+char\s*\*)\s*(mvlt_\w+)\s*\(([^()]*)\)\s*;", text):
+        params = [] if params.strip() == "void" else [norm(re.fullmatch(r"\s*(.*?[\s*])\w+\s*", q, flags=re.S).group(1)) for q in params.split(",")]
+        assert name not in protos
+        protos[name] = (norm(ret), params)
+    structs = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(mvlt_\w+)\s*\{(.*?)\}\s*\1\s*;", text, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):          # `const void* A`, `int M, N, K`, `mvlt_rowmap a_map, c_map`
+            m = re.fullmatch(r"(.*?[\s*])(\w+(?:\s*,\s*\w+)*)", decl, flags=re.S)
+            fields += [(f.strip(), norm(m.group(1))) for f in m.group(2).split(",")]
+        structs[name] = fields
+    return protos, structs
+
+
 def test_library_exports_every_declared_symbol():
+    """the library exports what the header declares, and the binding (mvlt_amd/_lib.py: PROTOTYPES, the Structure classes) states the header's prototypes and struct
+    layouts parameter by parameter and field by field: a swapped int / long pair or two swapped same-size fields fails here, not in a kernel"""
+    import ctypes as C
     import mvlt_amd._lib as L
     hdr = open(os.path.join(ROOT, "include", "mvlt_hip.h")).read()
     declared = set(re.findall(r"\b(mvlt_[a-z0-9_]+)\s*\(", hdr))
     assert len(declared) >= 20
     for name in sorted(declared):
         assert hasattr(L.lib, name), f"{name} declared in mvlt_hip.h but not exported by libmvlt_hip.so"
-    assert set(L.EXPORTS) <= declared
+    assert set(L.EXPORTS) == declared and len(L.EXPORTS) == len(declared)
     # the library, the header and the binding agree on the ABI version (ADVICE r4: signature-only changes used to go unnoticed)
     assert L.lib.mvlt_abi_version() == L.ABI_VERSION == int(re.search(r"#define MVLT_ABI_VERSION (\d+)", hdr).group(1))
     assert L.lib.mvlt_sizeof(b"no_such_struct") == -1
+
+    protos, structs = _header_abi(hdr)
+    assert set(protos) == declared and len(protos) == 61
+    classes = dict(L.STRUCTS)
+    assert set(structs) == set(classes) and len(classes) == 9
+    scalars = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "uint64_t": C.c_uint64}
+    is_pointer = lambda t: t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and issubclass(t, C._Pointer))
+    device_tables = {("mvlt_weight_prep", 0)}            # a `const mvlt_S*` that is a device address, not a host struct: bound as c_void_p
+
+    def matches(ctype, written, where):
+        if written in scalars:
+            return ctype is scalars[written]
+        if not written.endswith("*"):
+            return ctype is classes[written]             # a struct by value (mvlt_rowmap inside the GEMM / LayerNorm argument structs)
+        base = written[:-1].replace("const", "").strip()
+        if base in classes:
+            return ctype is C.c_void_p if where in device_tables else ctype is C.POINTER(classes[base])
+        return is_pointer(ctype)
+
+    for name, (ret, params) in protos.items():
+        restype, argtypes = L.PROTOTYPES[name]
+        fn = getattr(L.lib, name)
+        assert fn.restype is restype and list(fn.argtypes or []) == list(argtypes), name        # the table is what the library object carries
+        assert restype is {"int": C.c_int, "const char*": C.c_char_p}[ret], name
+        assert len(argtypes) == len(params), (name, len(argtypes), len(params))
+        for i, (ctype, written) in enumerate(zip(argtypes, params)):
+            assert matches(ctype, written, (name, i)), f"{name} parameter {i}: header says `{written}`, binding has {ctype.__name__}"
+    for name, fields in structs.items():
+        cls = classes[name]
+        assert [f for f, _ in cls._fields_] == [f for f, _ in fields], name
+        for (f, ctype), (_, written) in zip(cls._fields_, fields):
+            assert matches(ctype, written, None), f"{name}.{f}: header says `{written}`, binding has {ctype.__name__}"
+        assert C.sizeof(cls) == L.lib.mvlt_sizeof(name.encode()), name
 
 
 def test_bad_arguments_return_error_codes_not_crashes():
@@ -92,6 +147,46 @@ def test_no_cpu_fallback():
     with pytest.raises(MVLTError):
         x = torch.zeros(8, 64)
         ops.gemm_nt(x, x, x.clone(), 8, 8, 64, 64, 64, 64)
+
+
+def _cpu_refusal_cases():
+    """(wrapper name, call with CPU tensors of the dtypes its asserts want).  `dev(...)` stands for a tensor that IS on the device (ptr() accepts it; the call never
+    gets as far as the library): it fills the positions the wrapper used to check, so that the CPU tensor sits where nothing was checked."""
+    import types
+    f32, bf16, f16, u8, i32, i64 = torch.float32, torch.bfloat16, torch.float16, torch.uint8, torch.int32, torch.int64
+    z = lambda dt=f32, *shape: torch.zeros(*(shape or (4, 8)), dtype=dt)
+    dev = lambda dt=f32, *shape: types.SimpleNamespace(is_cuda=True, dtype=dt, shape=shape or (4, 8), data_ptr=lambda: 0)
+    return [
+        ("col_stats", lambda o: o.col_stats(z(), 8, 4, 8, z(), z())),
+        ("bn_finalize", lambda o: o.bn_finalize(z(), z(), 4, 8, 1e-5, 0.1, z(), z())),
+        ("bn_norm", lambda o: o.bn_norm(z(), 8, z(), z(), z(), z(), 4, 8, y32=z(), ld32=8)),
+        ("bn_finalize_norm", lambda o: o.bn_finalize_norm(z(f16), 8, z(), z(), 1, 1e-5, 0.1, z(), z(), None, None, z(), z(), 4, 8, y16=z(bf16), ld16=8)),
+        ("bn_bwd_reduce", lambda o: o.bn_bwd_reduce(z(), 8, z(), 8, z(), z(), 4, 8, z(), z())),
+        ("bn_bwd_apply", lambda o: o.bn_bwd_apply(z(), 8, z(), 8, z(), z(), z(), z(), z(), 4, 8, z(bf16), 8)),
+        ("ew_mul", lambda o: o.ew_mul(z(), 8, z(), 8, z(), 8, M=4, Cdim=8)),
+        ("ew_mul3_bwd", lambda o: o.ew_mul3_bwd(z(), 8, z(), z(), z(), 8, z(), z(), z(), 4, 8)),
+        ("upsample_fwd", lambda o: o.upsample_fwd(z(), 8, 1, 2, 2, 8, 2, z(f32, 16, 8), 8)),
+        ("upsample_bwd", lambda o: o.upsample_bwd(z(f32, 16, 8), 8, False, 1, 2, 2, 8, 2, z(), 8)),
+        ("add_column_sums", lambda o: o.add_column_sums(z(), z(f32, 4), z(f32, 4))),
+        ("head_grad_prep", lambda o: o.head_grad_prep(z(f32, 4, 6), z(bf16, 4, 8), z(f32, 6))),
+        ("weight_prep", lambda o: o.weight_prep(z(u8, 64), z(i32, 2), 1, 1, bf16)),
+        ("resize_bilinear_tokens_multi", lambda o: o.resize_bilinear_tokens_multi([(z(), z(f32, 16, 8), 2, 2, 4, 4, 8)])),
+        # a CPU tensor where the wrapper checked nothing before: pos / lse / decay_mask (ids, word, y / logits, labels, dlogits / p, g, m, v, hp were checked)
+        ("bert_embed_fwd", lambda o: o.bert_embed_fwd(dev(i64, 4), dev(f32, 16, 768), z(f32, 4, 768), z(f32, 768), z(f32, 768), z(f32, 768), None, 0.0,
+                                                      dev(bf16, 4, 768), z(f32, 4), z(f32, 4), 4, 4, 1e-12)),
+        ("cross_entropy_bwd", lambda o: o.cross_entropy_bwd(dev(), dev(i64, 4), z(f32, 4), z(f32, 1), z(f32, 1), dev(), 4, 8, 8, 8)),
+        ("adamw_step", lambda o: o.adamw_step(dev(f32, 8), dev(f32, 8), dev(f32, 8), dev(f32, 8), None, 8, dev(f32, 8), z(u8, 8))),
+    ]
+
+
+@pytest.mark.parametrize("name,call", _cpu_refusal_cases(), ids=[n for n, _ in _cpu_refusal_cases()])
+def test_cpu_tensor_is_refused_before_the_library(name, call):
+    """every tensor argument of every wrapper goes through ptr(): a host tensor raises there, it never reaches a kernel as a device address.  The message is
+    matched because on a machine without a GPU a launch that did go out ends in an MVLTError too -- from the failed launch, the path this rules out."""
+    from mvlt_amd import ops
+    from mvlt_amd._lib import MVLTError
+    with pytest.raises(MVLTError, match="no CPU fallback"):
+        call(ops)
 
 
 def test_loss_composition_equals_oracle():
