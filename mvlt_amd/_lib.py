@@ -1,4 +1,4 @@
-"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h).
+"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h).
 
 The product path has NO fallback: importing this module without the built library, or calling an op without a
 GPU, raises.  torch is used only for device memory and streams.
@@ -192,6 +192,23 @@ for _name, _cls in STRUCTS:
     _n = lib.mvlt_sizeof(_name.encode())
     if _n != C.sizeof(_cls):
         raise ImportError(f"ABI mismatch for {_name}: library says {_n} bytes, binding has {C.sizeof(_cls)}")
+
+# The entry points of include/mvlt_hip_ext.h: additions beside the ABI above (whose table and version stay as they are), bound the same way and checked
+# against their own version number (tests/test_guard_cpu.py compares this table with that header).
+EXT_PROTOTYPES = {
+    "mvlt_ext_version": (_i, []),
+    "mvlt_step_gate": (_i, [_vp, _i, _f, _f, _vp, _vp, _vp]),
+    "mvlt_adamw_step_gated": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp]),
+}
+for _name, (_res, _args) in EXT_PROTOTYPES.items():
+    if not hasattr(lib, _name):
+        raise ImportError(f"{LIB_PATH} does not export {_name} (include/mvlt_hip_ext.h): stale build? run python -m mvlt_amd.build")
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
+EXT_VERSION = 1          # include/mvlt_hip_ext.h MVLT_EXT_VERSION this binding was written against
+if lib.mvlt_ext_version() != EXT_VERSION:
+    raise ImportError(f"extension mismatch: {LIB_PATH} is version {lib.mvlt_ext_version()}, the binding is version {EXT_VERSION} (stale build? run python -m mvlt_amd.build)")
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 

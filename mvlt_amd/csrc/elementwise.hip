@@ -3,6 +3,7 @@
 // Everything is coalesced 16-byte traffic with fp32 math; none of this is reshaped into a GEMM.
 #include "common.h"
 #include "../../include/mvlt_hip.h"
+#include "../../include/mvlt_hip_ext.h"
 
 namespace {
 
@@ -434,10 +435,18 @@ __global__ __launch_bounds__(NT) void smooth_l1_grad_kernel(const float* pred, c
 // fine-tune run) costs that one read -- no load of p / g / m / v, no store; a vector without a frozen byte takes the loop body it always took.
 // Parameters start at 8-element offsets, so a mixed vector exists only where a frozen tensor's ragged tail meets its alignment gap (at most one
 // per tensor): it is stepped lane by lane with scalar stores, the frozen lanes are skipped.
+// GATED (mvlt_adamw_step_gated, include/mvlt_hip_ext.h): gscale_dev is the fp32[4] gate mvlt_step_gate left on the device -- {norm, coefficient, ok, 0}.
+// Every thread reads gate[2] FIRST (one uniform load); 0 = the step is skipped: the thread returns before it has touched p, g, m, v, p16 or the mask (the
+// GradScaler skip of reference engine_grid_masking.py:116-127, decided without a host read).  1 = the ungated kernel with gscale_dev = &gate[1], bit for bit.
+// GATED = false compiles to the kernel this was before the flag existed.
+template <bool GATED>
 __global__ __launch_bounds__(NT) void adamw_kernel(float* p, const float* g, float* m, float* v, bf16* p16, long n, const float* hp,
                                                    const uint8_t* decay_mask, const float* gscale_dev) {
+  if constexpr (GATED) {
+    if (gscale_dev[2] == 0.0f) return;
+  }
   const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], bc1 = hp[5], bc2 = hp[6];
-  const float gs = gscale_dev ? hp[7] * gscale_dev[0] : hp[7];
+  const float gs = GATED ? hp[7] * gscale_dev[1] : gscale_dev ? hp[7] * gscale_dev[0] : hp[7];
   const float step_size = lr / bc1;
   const float inv_sqrt_bc2 = rsqrtf(bc2);
   for (long i = ((long)blockIdx.x * NT + threadIdx.x) * 4; i < n; i += (long)gridDim.x * NT * 4) {
@@ -520,21 +529,52 @@ __global__ __launch_bounds__(NT) void grad_sumsq_kernel(const float* g, long n, 
 }
 // out[0] = total_norm = grad_scale * sqrt(sum of the partials), out[1] = min(1, max_norm / (total_norm + 1e-6)): clip_grad_norm_'s coefficient
 // (error_if_nonfinite=False: an infinite norm gives 0, a NaN norm gives NaN, as torch.clamp(max=1) does).  One workgroup, fixed order.
-__global__ __launch_bounds__(NT) void clip_coef_kernel(const float* partials, int n_partials, float grad_scale, float max_norm, float* out) {
-  __shared__ float s_w[NT / 64];
+// The fold of the partials, shared by clip_coef_kernel and step_gate_kernel so that both see the same sum in every bit: lane t adds partials[t], [t + NT], ...,
+// then the xor butterfly of the wave, then thread 0 adds the NT / 64 wave sums in order.  One workgroup of NT threads; the result is valid in thread 0 only.
+__device__ __forceinline__ float fold_partials(const float* partials, int n_partials, float* s_w) {
   float t = 0.f;
   for (int i = threadIdx.x; i < n_partials; i += NT) t += partials[i];
   t = wave_sum(t);
   if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = t;
   __syncthreads();
+  t = 0.f;
   if (threadIdx.x == 0) {
-    t = 0.f;
 #pragma unroll
     for (int w = 0; w < NT / 64; ++w) t += s_w[w];
+  }
+  return t;
+}
+__global__ __launch_bounds__(NT) void clip_coef_kernel(const float* partials, int n_partials, float grad_scale, float max_norm, float* out) {
+  __shared__ float s_w[NT / 64];
+  const float t = fold_partials(partials, n_partials, s_w);
+  if (threadIdx.x == 0) {
     const float norm = __fmul_rn(grad_scale, sqrtf(t));                  // (rounded before the 1e-6 is added, like torch's fp32 tensor)
     const float coef = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));
     out[0] = norm;
     out[1] = coef > 1.0f ? 1.0f : coef;                                  // keeps a NaN (fminf would drop it)
+  }
+}
+// The step gate (mvlt_step_gate, include/mvlt_hip_ext.h): the norm of clip_coef_kernel, in the same bits, plus the decision timm's NativeScaler / GradScaler
+// takes on the host at reference engine_grid_masking.py:116-127 -- a non-finite norm means "do not step".  out = {norm, coefficient, ok, 0}: the coefficient
+// is exactly 0 when the norm is not finite, clip_grad_norm_'s when max_norm > 0, exactly 1 otherwise.  counters = {applied, skipped}, bumped by thread 0 with a
+// plain load and store (one workgroup, launches ordered by the stream: no atomics).
+__global__ __launch_bounds__(NT) void step_gate_kernel(const float* partials, int n_partials, float grad_scale, float max_norm, float* out, int* counters) {
+  __shared__ float s_w[NT / 64];
+  const float t = fold_partials(partials, n_partials, s_w);
+  if (threadIdx.x == 0) {
+    const float norm = __fmul_rn(grad_scale, sqrtf(t));
+    const bool ok = (__float_as_uint(norm) & 0x7f800000u) != 0x7f800000u;        // neither Inf nor NaN
+    float coef = 1.0f;
+    if (max_norm > 0.0f) {
+      coef = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));
+      coef = coef > 1.0f ? 1.0f : coef;
+    }
+    out[0] = norm;
+    out[1] = ok ? coef : 0.0f;
+    out[2] = ok ? 1.0f : 0.0f;
+    out[3] = 0.0f;
+    if (ok) counters[0] = counters[0] + 1;
+    else counters[1] = counters[1] + 1;
   }
 }
 // x[i] *= factor_dev[0].  A factor of exactly 1 (the clip did not bite) skips the pass: decided on the device, the same for every lane; x * 1.0f == x bit for bit.
@@ -995,8 +1035,26 @@ extern "C" int mvlt_adamw_step(float* p, const float* g, float* m, float* v, voi
                                const uint8_t* decay_mask, const float* gscale_dev, void* stream) {
   MVLT_REQUIRE(p && g && m && v && hp && n >= 0 && n % 4 == 0, "mvlt_adamw_step: bad arguments (n must be a multiple of 4)");
   if (n == 0) return MVLT_OK;
-  MVLT_LAUNCH(adamw_kernel, dim3(grid_for(n / 4, 8192)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, hp, decay_mask, gscale_dev);
+  MVLT_LAUNCH((adamw_kernel<false>), dim3(grid_for(n / 4, 8192)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, hp, decay_mask, gscale_dev);
   return mvlt_check_launch("mvlt_adamw_step");
+}
+
+// ---- include/mvlt_hip_ext.h
+extern "C" int mvlt_ext_version(void) { return MVLT_EXT_VERSION; }
+
+extern "C" int mvlt_adamw_step_gated(float* p, const float* g, float* m, float* v, void* p_bf16, long n, const float* hp,
+                                     const uint8_t* decay_mask, const float* gate, void* stream) {
+  MVLT_REQUIRE(p && g && m && v && hp && gate && n >= 0 && n % 4 == 0, "mvlt_adamw_step_gated: bad arguments (null pointer, or n is not a multiple of 4)");
+  if (n == 0) return MVLT_OK;
+  MVLT_LAUNCH((adamw_kernel<true>), dim3(grid_for(n / 4, 8192)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16, n, hp, decay_mask, gate);
+  return mvlt_check_launch("mvlt_adamw_step_gated");
+}
+
+extern "C" int mvlt_step_gate(const float* partials, int n_partials, float grad_scale, float max_norm, float* out, int* counters, void* stream) {
+  MVLT_REQUIRE(partials && out && counters, "mvlt_step_gate: null pointer (partials, out and counters are required)");
+  MVLT_REQUIRE(n_partials >= 1 && n_partials <= 1024, "mvlt_step_gate: n_partials must be in [1, 1024], got %d", n_partials);
+  MVLT_LAUNCH(step_gate_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, partials, n_partials, grad_scale, max_norm, out, counters);
+  return mvlt_check_launch("mvlt_step_gate");
 }
 
 extern "C" int mvlt_grad_sumsq(const float* g, long n, const uint8_t* mask, float* partials, int n_partials, void* stream) {

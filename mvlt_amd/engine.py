@@ -256,7 +256,8 @@ def train_one_epoch_vl(model, criterion, data_loader, optimizer, device, epoch, 
         vals = readback.get()                  # waits for this iteration's forward only; backward + step are already queued
         if not math.isfinite(vals[0]):
             print(f" [ Warning!!! ] Total Loss is {vals[0]} (loss_mlm={vals[1]} | loss_itm={vals[2]} | loss_sup_cls={vals[3]} | "
-                  f"loss_sub_cls={vals[4]} | loss_t2i={vals[5]}), non-finite value")
+                  f"loss_sub_cls={vals[4]} | loss_t2i={vals[5]}), non-finite value"
+                  + (" -- the step is guarded: non-finite gradients skip the optimizer step" if getattr(loss_scaler, "skip_nonfinite", False) else ""))
         logger.update(**dict(zip(LOSS_KEYS, vals)))
         logger.update(lr=optimizer.param_groups[0]["lr"])
     logger.synchronize_between_processes(device)
@@ -270,12 +271,19 @@ train_one_epoch = train_one_epoch_vl      # BASELINE.json's north_star calls it 
 class BF16Scaler:
     """loss_scaler for bf16 training: the callable / state_dict interface of timm.utils.NativeScaler
     (reference main_vl.py:309,346,426,453; engine_grid_masking.py:126) without fp16 loss scaling, which bf16 does
-    not need.  `_scaler` exists because main_vl.py:426 re-assigns it every epoch."""
+    not need.  `_scaler` exists because main_vl.py:426 re-assigns it every epoch.
+
+    skip_nonfinite=True brings back the one thing of the GradScaler that bf16 still wants (docs/nonfinite_guard.md): a backward pass that left Inf / NaN in a
+    gradient does not step the optimizer (reference engine_grid_masking.py:116-127).  With a FusedAdamW the decision is taken and obeyed on the device
+    (FlatStore.gate_grads, no host read; FusedAdamW.skipped_steps counts); with any other optimizer it costs one host read of the total norm per
+    step, as a GradScaler does, and `skipped_steps` here counts."""
     state_dict_key = "amp_scaler"
 
-    def __init__(self):
+    def __init__(self, skip_nonfinite=False):
         self._scaler = None
-        self.last_grad_norm = None        # total gradient norm of the last call as a 0-dim DEVICE tensor (fused clipping only; None when no clipping ran)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.skipped_steps = 0            # steps this scaler skipped on the HOST path (a stock optimizer); the fused path counts on the device
+        self.last_grad_norm = None        # total gradient norm of the last call as a 0-dim DEVICE tensor (fused clipping / gating only; None otherwise)
 
     def __call__(self, loss, optimizer, clip_grad=None, parameters=None, create_graph=False):
         # The data-parallel mean's 1/world may ride in the fused AdamW kernel instead of being a pass over G -- but only HERE, where
@@ -290,7 +298,18 @@ class BF16Scaler:
             loss.backward(create_graph=create_graph)
             # main_vl.py passes --clip-grad (default None = no clipping).  timm's NativeScaler tests `is not None`, so the engine's
             # own default max_norm=0 would scale every gradient to zero there; here 0 means "no clipping" as well.
-            if clip_grad and store is not None:
+            if self.skip_nonfinite and store is not None:
+                # the norm pass of the clipping below, plus the decision: ok / coefficient stay on the device and the gated AdamW kernel obeys them
+                # (clip_grad None / 0: the coefficient is exactly 1)
+                self.last_grad_norm = store.gate_grads(clip_grad or None)
+            elif self.skip_nonfinite:
+                assert parameters is not None
+                parameters = list(parameters)
+                norm = torch.nn.utils.clip_grad_norm_(parameters, clip_grad if clip_grad else float("inf"))
+                if not math.isfinite(float(norm)):               # the one host read of this path (GradScaler.step pays the same)
+                    self.skipped_steps += 1
+                    return
+            elif clip_grad and store is not None:
                 # one read of the flat gradient buffer for the global norm; the coefficient stays on the device and rides in the AdamW kernel beside
                 # the 1/world: G is not rewritten, nothing is read back (FlatStore.clip_grad_norm)
                 self.last_grad_norm = store.clip_grad_norm(clip_grad)
@@ -302,7 +321,7 @@ class BF16Scaler:
         finally:
             if store is not None:
                 store.scale_in_optimizer = False
-                store.apply_pending_scale()                                    # nothing owed outside this call, 1/world or clip (a step that raised)
+                store.apply_pending_scale()                                    # nothing owed outside this call, 1/world, clip or gate (a step that raised)
 
     def state_dict(self):
         return {}

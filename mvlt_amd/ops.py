@@ -264,6 +264,23 @@ def clip_coef(partials, grad_scale, max_norm, out):
     check(L.lib.mvlt_clip_coef(ptr(partials), partials.numel(), float(grad_scale), float(max_norm), ptr(out), stream_ptr()), "mvlt_clip_coef")
 
 
+def step_gate(partials, grad_scale, max_norm, out, counters):
+    """out[0:4] = [norm, coefficient, ok, 0] from the partials of `grad_sumsq`: norm = grad_scale * sqrt(sum(partials)) in `clip_coef`'s bits, ok = 1.0 when
+    it is finite else 0.0, coefficient = 0 when it is not finite, min(1, max_norm / (norm + 1e-6)) when max_norm > 0, else 1.  counters (int32[2], device,
+    kept by the caller from step to step): [0] += ok, [1] += not ok.  The gate `adamw_step_gated` obeys (include/mvlt_hip_ext.h)."""
+    assert partials.dtype == torch.float32 and out.dtype == torch.float32 and out.numel() >= 4 and out.is_contiguous() and partials.is_contiguous()
+    assert counters.dtype == torch.int32 and counters.numel() >= 2 and counters.is_contiguous()
+    check(L.lib.mvlt_step_gate(ptr(partials), partials.numel(), float(grad_scale), float(max_norm), ptr(out), ptr(counters), stream_ptr()), "mvlt_step_gate")
+
+
+def adamw_step_gated(p, g, m, v, p16, n, hp, decay_mask, gate):
+    """`adamw_step` under the gate of `step_gate`: gate[2] == 0 -> no load or store of p / g / m / v / p16 / decay_mask at all (the step is skipped on the
+    device); gate[2] == 1 -> adamw_step(..., gscale_dev=gate[1:2]) bit for bit"""
+    assert decay_mask is None or decay_mask.dtype == torch.uint8
+    assert gate.dtype == torch.float32 and gate.numel() >= 4 and gate.is_contiguous()
+    check(L.lib.mvlt_adamw_step_gated(ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), n, ptr(hp), ptr(decay_mask), ptr(gate), stream_ptr()), "mvlt_adamw_step_gated")
+
+
 def scale_by_dev(x, n, factor_dev):
     """x[0:n] *= factor_dev[0] (an fp32 device scalar; exactly 1 skips the pass on the device)"""
     assert x.dtype == torch.float32 and factor_dev.dtype == torch.float32 and x.is_contiguous() and x.numel() >= n

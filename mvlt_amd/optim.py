@@ -10,6 +10,10 @@ no-decay group and `[1]` the decay group, like timm's add_weight_decay.
 Frozen parameters (requires_grad=False) are left alone, as torch.optim.AdamW leaves a parameter without `.grad` alone: the groups hold every
 parameter of the model, and the per-element mask of the kernel carries a third value for the elements of frozen ones (neither they nor their
 moments nor their bf16 copies are written).  The mask follows requires_grad from step to step, so un-freezing needs no new optimizer.
+
+skip_nonfinite=True (docs/nonfinite_guard.md): with engine.BF16Scaler(skip_nonfinite=True) in front, a step whose gradients hold Inf / NaN changes nothing
+-- the decision is taken on the device (FlatStore.gate_grads) and obeyed by the kernel, the host never reads it.  One difference from GradScaler follows:
+`_step`, the host count behind the bias corrections, counts ATTEMPTED steps, so after a skip the corrections are those of t + 1.
 """
 import torch
 
@@ -27,8 +31,8 @@ def phased_ranges(S):
     issued DURING the backward pass -- by now (mostly) complete -- then the ones issued at its end, each group after `wait()` on its works (a
     stream-side wait for RCCL: the host keeps enqueuing).  The first launch then runs while the tail is still on the wire; element-wise AdamW makes the
     result bit-identical to one launch over everything.  Anything the collectives do not cover exactly once falls back to wait-all + one range.
-    With a clip pending (FlatStore.clip_grad_norm ran: the global norm needs every gradient) the collectives are already waited and this yields the
-    single whole range."""
+    With a clip or a step gate pending (FlatStore.clip_grad_norm / gate_grads ran: the global norm needs every gradient) the collectives are already
+    waited and this yields the single whole range."""
     works, S.grad_works = S.grad_works, []
     if not works:
         yield 0, S.total
@@ -69,9 +73,11 @@ def clip_grad_norm_(model, max_norm):
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, skip_nonfinite=False):
         model = _unwrap(model)
         self.model = model
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._pending_counts = None           # (applied, skipped) of a checkpoint loaded before the flat store exists
         no_decay, decay = [], []
         # every parameter of the model is in a group, frozen ones too: `requires_grad` decides per step (the mask byte of mvlt_adamw_step), so a
         # parameter frozen now and un-frozen later starts stepping without a new optimizer
@@ -106,6 +112,9 @@ class FusedAdamW(torch.optim.Optimizer):
             # next forward behind an idle GPU (1.3 ms per fine-tune step, tools/host_time.py).  An event per row guards its reuse.
             self._hp_pin = torch.zeros(4, 8).pin_memory() if S.P.is_cuda else None
             self._hp_ev = [None] * 4
+        if self._pending_counts is not None:     # step counters of a checkpoint that was loaded before the first forward
+            S._gate_buffers()[1].copy_(torch.tensor(self._pending_counts, dtype=torch.int32))
+            self._pending_counts = None
         key = (S.P.data_ptr(), tuple(p.requires_grad for p in S._plist))
         if self._mask_key != key:                # the store was re-materialised, or a parameter was frozen / un-frozen (as FlatStore's norm mask)
             # one byte per element: 1 = weight decay applies (timm's split: not for 1-D tensors / biases), 0 = it does not (alignment gaps too),
@@ -143,6 +152,9 @@ class FusedAdamW(torch.optim.Optimizer):
         assert g0["lr"] == g1["lr"], "FusedAdamW steps both param groups with one learning rate (as timm's scheduler sets them)"
         gscale, S.pending_grad_scale = S.pending_grad_scale, 1.0      # 1/world of the data-parallel mean, applied in the kernel
         clip, S.pending_clip = S.pending_clip, None                   # clip coefficient (device scalar) of FlatStore.clip_grad_norm: one more factor in the kernel
+        gate, S.pending_gate = S.pending_gate, None                   # [norm, coef, ok, 0] of FlatStore.gate_grads: the gated kernel obeys ok and applies coef
+        if gate is not None and clip is not None:
+            raise RuntimeError("FusedAdamW: both a clip and a step gate are pending (FlatStore.gate_grads(max_norm) does the clipping itself)")
         row = [g0["lr"], b1, b2, g0["eps"], g1["weight_decay"], 1 - b1 ** self._step, 1 - b2 ** self._step, gscale]
         if self._hp_pin is None:
             self._hp.copy_(torch.tensor(row, dtype=torch.float32))
@@ -157,6 +169,10 @@ class FusedAdamW(torch.optim.Optimizer):
         for lo, hi in phased_ranges(S):
             if self._all_frozen(lo, hi):         # nothing in the range steps: no launch
                 continue
+            if gate is not None:                 # (gate_grads waited for every collective: this is the single whole range)
+                ops.adamw_step_gated(S.P[lo:hi], S.G[lo:hi], self._m[lo:hi], self._v[lo:hi], None if S.C is None else S.C[lo:hi], hi - lo, self._hp,
+                                     self._wd_mask[lo:hi], gate)
+                continue
             ops.adamw_step(S.P[lo:hi], S.G[lo:hi], self._m[lo:hi], self._v[lo:hi], None if S.C is None else S.C[lo:hi], hi - lo, self._hp, self._wd_mask[lo:hi],
                            gscale_dev=clip)
         # W^T / permuted conv operand copies are refreshed by the next forward; the plain bf16 copy S.C is already current,
@@ -168,10 +184,32 @@ class FusedAdamW(torch.optim.Optimizer):
     def zero_grad(self, set_to_none=True):
         super().zero_grad(set_to_none=set_to_none)
 
+    def _counts(self):
+        """(applied, skipped): the device counters of FlatStore.gate_grads (one read-back), or what a checkpoint left while there is no store yet"""
+        if self._pending_counts is not None:
+            return self._pending_counts
+        S = self.model.store
+        if getattr(S, "_gate", None) is None:
+            return (0, 0)
+        a, k = S._gate[1].tolist()
+        return (a, k)
+
+    @property
+    def applied_steps(self):
+        """guarded steps that were applied (finite gradient norm).  Reads the device: for logging, not for the step path"""
+        return self._counts()[0]
+
+    @property
+    def skipped_steps(self):
+        """guarded steps the device skipped (Inf / NaN in a trainable gradient).  Reads the device: for logging, not for the step path"""
+        return self._counts()[1]
+
     def state_dict(self):
         sd = super().state_dict()
         m, v = (self._m, self._v) if self._m is not None else (self._pending or (None, None))
         sd["fused"] = dict(step=self._step, m=None if m is None else m.cpu(), v=None if v is None else v.cpu())
+        if self.skip_nonfinite:
+            sd["fused"]["applied"], sd["fused"]["skipped"] = self._counts()
         return sd
 
     def load_state_dict(self, sd):
@@ -182,6 +220,13 @@ class FusedAdamW(torch.optim.Optimizer):
         super().load_state_dict(sd)
         if fused is not None:
             self._step = fused["step"]
+            if "applied" in fused or "skipped" in fused:       # checkpoints of a guarded run carry the counters; others leave them as they are
+                counts = (int(fused.get("applied", 0)), int(fused.get("skipped", 0)))
+                if self.model.store.P is not None:
+                    self._pending_counts = None
+                    self.model.store._gate_buffers()[1].copy_(torch.tensor(counts, dtype=torch.int32))
+                else:
+                    self._pending_counts = counts
             if fused["m"] is not None:
                 if self.model.store.P is not None:
                     self._pending = None

@@ -147,6 +147,8 @@ class FlatStore:
         self.pending_grad_scale = 1.0     # factor still owed to G (1/world after a data-parallel SUM all-reduce)
         self.pending_clip = None          # clip coefficient still owed to G: a 1-element fp32 DEVICE tensor (clip_grad_norm), applied by FusedAdamW's kernel
         self._clip = None                 # (key, norm mask, partials, [norm, coef]) of clip_grad_norm, allocated once per store
+        self.pending_gate = None          # step gate still owed to G: the fp32[4] DEVICE tensor [norm, coef, ok, 0] of gate_grads, obeyed by FusedAdamW's gated kernel
+        self._gate = None                 # ([norm, coef, ok, 0], int32 [applied, skipped]) of gate_grads; the counters live as long as the store
         # gradient collectives still in flight when the backward pass returned: [(work, lo, hi, g_view, payload or None, early)].  Only set while
         # `scale_in_optimizer` (the fused optimizer is the next reader: it steps the ranges whose collectives are done while the tail is on the
         # wire, FusedAdamW.step); every other reader of G goes through wait_grads() first.
@@ -348,6 +350,7 @@ class FlatStore:
             self.G.zero_()
             self.pending_grad_scale = 1.0
             self.pending_clip = None           # a clip nobody stepped belongs to gradients that are gone
+            self.pending_gate = None           # and so does a gate
         else:
             # mixed state (a zero_grad over a subset of the parameters, or p.grad = None on some): decided per parameter, like torch --
             # the slices whose .grad aliases keep their running sum, the others start from zero (the any-alias rule of round 3
@@ -569,6 +572,10 @@ class FlatStore:
         if self.pending_clip is not None:
             clip, self.pending_clip = self.pending_clip, None
             ops.scale_by_dev(self.G, self.total, clip)      # (skips the pass on the device when the clip did not bite)
+        if self.pending_gate is not None:
+            # the gate's coefficient, like a clip's.  On a skipped step it is 0 and G holds Inf / NaN: 0 * Inf = NaN -- the gradients of a skipped step are void
+            gate, self.pending_gate = self.pending_gate, None
+            ops.scale_by_dev(self.G, self.total, gate[1:2])
 
     # ---- gradient clipping on the flat buffer ------------------------------------------------------------------------------
     CLIP_PARTIALS = 1024          # workgroups of the sum-of-squares launch (4 per CU: 40 M gradients = 39 16-byte loads per lane)
@@ -600,12 +607,42 @@ class FlatStore:
         norm as a 0-dim device tensor (a view of the store's persistent [norm, coef] pair: the next call overwrites it)."""
         self.wait_grads()
         self.sync_grads()
-        if self.pending_clip is not None:                   # a second clipping sees the gradients the first one left
+        if self.pending_clip is not None or self.pending_gate is not None:      # a second clipping sees the gradients the first one left
             self.apply_pending_scale()
         mask, part, out = self._clip_buffers()
         ops.grad_sumsq(self.G, self.total, mask, part)
         ops.clip_coef(part, self.pending_grad_scale, max_norm, out)
         self.pending_clip = out[1:2]
+        return out[0]
+
+    # ---- skip the step on non-finite gradients, decided on the device (docs/nonfinite_guard.md) ------------------------------
+    def _gate_buffers(self):
+        """([norm, coef, ok, 0] fp32, [applied, skipped] int32) on G's device; the counters are created once (zero) and move with the store"""
+        dev = self.G.device
+        if self._gate is None:
+            self._gate = (torch.zeros(4, device=dev, dtype=torch.float32), torch.zeros(2, device=dev, dtype=torch.int32))
+        elif self._gate[0].device != dev:
+            self._gate = (self._gate[0].to(dev), self._gate[1].to(dev))
+        return self._gate
+
+    @torch.no_grad()
+    def gate_grads(self, max_norm=None):
+        """What a GradScaler decides on the host (reference engine_grid_masking.py:126: no optimizer step after a backward pass that left Inf / NaN in a
+        gradient), decided on the device and never read back: one pass over G for the global norm of the trainable elements (the mask and the sum of
+        clip_grad_norm, `pending_grad_scale` inside the norm and still owed), then one small launch that leaves `pending_gate` = [norm, coef, ok, 0] for
+        FusedAdamW's gated kernel and counts the step as applied or skipped.  coef is the clip coefficient for `max_norm` (None / 0: exactly 1, no
+        clipping) when the norm is finite; when it is not, ok = 0 and coef = 0: the kernel touches nothing.  G keeps its non-finite values then -- the
+        gradients of a skipped step are void, also for apply_pending_scale().  Returns the norm as a 0-dim device tensor (a view of the persistent
+        record: the next call overwrites it)."""
+        self.wait_grads()
+        self.sync_grads()
+        if self.pending_clip is not None or self.pending_gate is not None:      # a second pass sees the gradients the first one left
+            self.apply_pending_scale()
+        mask, part, _ = self._clip_buffers()
+        out, counters = self._gate_buffers()
+        ops.grad_sumsq(self.G, self.total, mask, part)
+        ops.step_gate(part, self.pending_grad_scale, max_norm or 0.0, out, counters)
+        self.pending_gate = out
         return out[0]
 
     def sync_grads(self):
