@@ -255,6 +255,12 @@ __global__ __launch_bounds__(NT) void scatter_rows_kernel(const T* src, const in
 // ------------------------------------------------------------------ cross entropy over rows (one workgroup per row)
 // fwd : lse[r] = logsumexp(logits[r,:]); loss_sum += (lse - logits[r,label]) for label != ignore; count += 1
 // bwd : dlogits[r,c] = (exp(logits - lse) - [c==label]) * gscale[0] / max(count,1)   (0 for ignored rows)
+// -inf logits (masked classes, as F.cross_entropy takes them): a running maximum that is still -inf would make every `x - max` of the (max, sum) update
+// -inf - -inf = NaN.  While the maximum is -inf, 0 is subtracted instead: every term is then exp(-inf) = 0 and the sum stays 0 until the first finite
+// logit arrives, so a row with at least one finite logit gets its exact lse wherever the -inf columns lie (one compare + select per update).
+// Outside the contract, as in the backward: a row of nothing but -inf (lse = -inf) and a label on a -inf column (an infinite loss).
+__device__ __forceinline__ float ce_shift(float running_max) { return running_max == -INFINITY ? 0.f : running_max; }
+
 template <typename T>
 __global__ __launch_bounds__(NT) void ce_fwd_kernel(const T* logits, const long* labels, long ignore, float* lse, float* loss_sum, float* count,
                                                     int rows, int V, int ld) {
@@ -278,16 +284,18 @@ __global__ __launch_bounds__(NT) void ce_fwd_kernel(const T* logits, const long*
         float nm = m;
 #pragma unroll
         for (int u = 0; u < U; ++u) nm = fmaxf(nm, fmaxf(fmaxf(x[u][0], x[u][1]), fmaxf(x[u][2], x[u][3])));
+        const float sub = ce_shift(nm);
         float a = 0.f;
 #pragma unroll
-        for (int u = 0; u < U; ++u) a += (__expf(x[u][0] - nm) + __expf(x[u][1] - nm)) + (__expf(x[u][2] - nm) + __expf(x[u][3] - nm));
-        s = s * __expf(m - nm) + a;
+        for (int u = 0; u < U; ++u) a += (__expf(x[u][0] - sub) + __expf(x[u][1] - sub)) + (__expf(x[u][2] - sub) + __expf(x[u][3] - sub));
+        s = s * __expf(m - sub) + a;
         m = nm;
       }
       for (; c < V4; c += NT * 4) {
         const f32x4 x = *(const f32x4*)((const float*)lr + c);
         const float nm = fmaxf(m, fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
-        s = s * __expf(m - nm) + (__expf(x[0] - nm) + __expf(x[1] - nm)) + (__expf(x[2] - nm) + __expf(x[3] - nm));
+        const float sub = ce_shift(nm);
+        s = s * __expf(m - sub) + (__expf(x[0] - sub) + __expf(x[1] - sub)) + (__expf(x[2] - sub) + __expf(x[3] - sub));
         m = nm;
       }
       c_first = V4;
@@ -296,7 +304,8 @@ __global__ __launch_bounds__(NT) void ce_fwd_kernel(const T* logits, const long*
   for (int c = c_first + threadIdx.x; c < V; c += NT) {
     float x = (float)lr[c];
     float nm = fmaxf(m, x);
-    s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + __expf(x - nm);
+    const float sub = ce_shift(nm);
+    s = s * __expf(m - sub) + __expf(x - sub);
     m = nm;
   }
   // combine (m, s) pairs: wave, then block
@@ -304,7 +313,8 @@ __global__ __launch_bounds__(NT) void ce_fwd_kernel(const T* logits, const long*
   for (int o = 32; o > 0; o >>= 1) {
     float om = __shfl_xor(m, o), os = __shfl_xor(s, o);
     float nm = fmaxf(m, om);
-    s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (om == -INFINITY ? 0.f : os * __expf(om - nm));
+    const float sub = ce_shift(nm);
+    s = s * __expf(m - sub) + os * __expf(om - sub);
     m = nm;
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -314,7 +324,8 @@ __global__ __launch_bounds__(NT) void ce_fwd_kernel(const T* logits, const long*
     float M = s_m[0], S = s_s[0];
     for (int w = 1; w < NT / 64; ++w) {
       float nm = fmaxf(M, s_m[w]);
-      S = (M == -INFINITY ? 0.f : S * __expf(M - nm)) + (s_m[w] == -INFINITY ? 0.f : s_s[w] * __expf(s_m[w] - nm));
+      const float sub = ce_shift(nm);
+      S = S * __expf(M - sub) + s_s[w] * __expf(s_m[w] - sub);
       M = nm;
     }
     lse[row] = M + logf(S);
