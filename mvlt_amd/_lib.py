@@ -1,4 +1,4 @@
-"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h).
+"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h and include/mvlt_hip_ema.h).
 
 The product path has NO fallback: importing this module without the built library, or calling an op without a
 GPU, raises.  torch is used only for device memory and streams.
@@ -209,6 +209,23 @@ for _name, (_res, _args) in EXT_PROTOTYPES.items():
 EXT_VERSION = 1          # include/mvlt_hip_ext.h MVLT_EXT_VERSION this binding was written against
 if lib.mvlt_ext_version() != EXT_VERSION:
     raise ImportError(f"extension mismatch: {LIB_PATH} is version {lib.mvlt_ext_version()}, the binding is version {EXT_VERSION} (stale build? run python -m mvlt_amd.build)")
+
+# The entry points of include/mvlt_hip_ema.h (the fused weight EMA, docs/ema.md): a third table, bound and version-checked like the one above
+# (tests/test_ema_cpu.py compares it with that header).
+EMA_PROTOTYPES = {
+    "mvlt_ema_version": (_i, []),
+    "mvlt_ema_update": (_i, [_vp, _vp, _vp, _l, _f, _f, _vp, _vp]),
+    "mvlt_ema_update_buffers": (_i, [_vp, _i, _f, _f, _vp]),             # table: a DEVICE array of int64[n][4]
+}
+for _name, (_res, _args) in EMA_PROTOTYPES.items():
+    if not hasattr(lib, _name):
+        raise ImportError(f"{LIB_PATH} does not export {_name} (include/mvlt_hip_ema.h): stale build? run python -m mvlt_amd.build")
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
+EMA_VERSION = 1          # include/mvlt_hip_ema.h MVLT_EMA_VERSION this binding was written against
+if lib.mvlt_ema_version() != EMA_VERSION:
+    raise ImportError(f"EMA entry points mismatch: {LIB_PATH} is version {lib.mvlt_ema_version()}, the binding is version {EMA_VERSION} (stale build? run python -m mvlt_amd.build)")
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 

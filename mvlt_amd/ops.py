@@ -281,6 +281,23 @@ def adamw_step_gated(p, g, m, v, p16, n, hp, decay_mask, gate):
     check(L.lib.mvlt_adamw_step_gated(ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), n, ptr(hp), ptr(decay_mask), ptr(gate), stream_ptr()), "mvlt_adamw_step_gated")
 
 
+def ema_update(ema, p, ema16, n, decay, one_minus_decay, mask=None):
+    """ema[0:n] = ema * decay + p * one_minus_decay, the two products and the sum each rounded to fp32 on its own (timm's ModelEma formula in torch's
+    bits); ema16 (bf16, optional) receives the bf16 of the new values in the same pass; mask (uint8, optional): elements whose byte is ADAMW_FROZEN are
+    left alone in ema and ema16.  Both factors go by value (include/mvlt_hip_ema.h)."""
+    assert ema.dtype == torch.float32 and p.dtype == torch.float32 and ema.is_contiguous() and p.is_contiguous() and ema.numel() >= n and p.numel() >= n
+    assert ema16 is None or (ema16.dtype == torch.bfloat16 and ema16.is_contiguous() and ema16.numel() >= n)
+    assert mask is None or (mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() >= n)
+    check(L.lib.mvlt_ema_update(ptr(ema), ptr(p), ptr(ema16), n, float(decay), float(one_minus_decay), ptr(mask), stream_ptr()), "mvlt_ema_update")
+
+
+def ema_update_buffers(table, n_tensors, decay, one_minus_decay):
+    """one launch over a device table int64[n_tensors][4] = {dst address, src address, numel, kind}: kind 0 = fp32, averaged like `ema_update`; kind 1 =
+    int64, copied (include/mvlt_hip_ema.h)"""
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() >= 4 * n_tensors
+    check(L.lib.mvlt_ema_update_buffers(ptr(table), n_tensors, float(decay), float(one_minus_decay), stream_ptr()), "mvlt_ema_update_buffers")
+
+
 def scale_by_dev(x, n, factor_dev):
     """x[0:n] *= factor_dev[0] (an fp32 device scalar; exactly 1 skips the pass on the device)"""
     assert x.dtype == torch.float32 and factor_dev.dtype == torch.float32 and x.is_contiguous() and x.numel() >= n

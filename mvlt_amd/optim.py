@@ -236,3 +236,167 @@ class FusedAdamW(torch.optim.Optimizer):
                 else:
                     self._m = self._v = None
                     self._pending = (fused["m"].detach().clone(), fused["v"].detach().clone())
+
+
+class FusedModelEma:
+    """Exponential moving average of a model's weights, kept by one HIP launch per step over the two flat parameter stores (docs/ema.md).  It stands where
+    timm.utils.ModelEma would (reference main_vl.py:16,295; engine_grid_masking.py:130-131 calls `model_ema.update(model)` after every optimizer step):
+
+        model_ema = FusedModelEma(model, decay=0.9999)
+        train_one_epoch_vl(model, ..., model_ema=model_ema)          # engine.py calls model_ema.update(model)
+        evaluate_vl(loader, model_ema.ema, device)                   # the averaged model is a model like any other
+        torch.save({"model_ema": model_ema.state_dict()}, path)      # what get_state_dict(model_ema) would store (main_vl.py:452)
+
+    `.ema` (alias `.module`, as in timm's ModelEmaV2) is a second model of the same class in eval mode, with a flat store of its own and parameters that take no
+    gradient.  `model`: the model or a data-parallel wrapper around it.  `update(model)` computes, for every parameter element and every floating buffer,
+    ema = ema * decay + model * (1 - decay) -- the two products and the sum each rounded to fp32, the bits of timm's per-tensor loop -- and writes the bf16
+    copy the averaged model computes with in the same pass.  `decay` is a plain attribute (change it between steps); `updates` counts the calls; with
+    warmup=True update number t = 1, 2, ... uses min(decay, (1 + t) / (10 + t)).
+
+    Two differences from timm.  (1) Integer buffers -- BatchNorm's num_batches_tracked -- are COPIED from the model: timm's formula, applied to an int64 tensor,
+    truncates the average back to an integer and leaves the counter one behind for ever.  (2) The elements of parameters the model holds frozen
+    (requires_grad=False at the time of the update, as FusedAdamW reads it) are left alone: they keep the value they were copied with, which is the model's.
+    timm averages them too, which moves e * decay + e * (1 - decay) away from e by a rounding now and then.
+
+    The update always happens: after a step the non-finite guard skipped (FusedAdamW(skip_nonfinite=True)) the average still moves towards the unchanged
+    parameters, as timm's does behind a GradScaler that skipped -- the engine calls update() unconditionally.
+
+    The source's store is built lazily, so the averaged model's is too: at the first update() on the source's device, or by the averaged model's own first
+    forward.  Until then its parameters are ordinary tensors, which is where load_state_dict() before the first forward puts a checkpoint -- nothing is kept
+    aside, and the store picks the values up when it is built.  There is no CPU path: update() on host tensors raises MVLTError."""
+
+    def __init__(self, model, decay=0.9999, warmup=False):
+        import copy
+        src = _unwrap(model)
+        S = src.store
+        # a deep copy of the module tree (names, shapes, order, values, buffers, tied weights) WITHOUT the source's store -- its flat buffers, gradient buffer,
+        # scratch and data-parallel hooks are not the copy's business -- and without what the schedule caches on the model between passes
+        memo = {id(S): None}
+        for k in ("_plan", "_pool_token", "_mim_fold"):
+            if src.__dict__.get(k) is not None:
+                memo[id(src.__dict__[k])] = None
+        self.ema = copy.deepcopy(src, memo)
+        slots = [k for k, v in vars(src).items() if v is S]
+        if not slots:
+            raise RuntimeError("FusedModelEma: the model does not hold its FlatStore as an attribute")
+        from .params import FlatStore
+        for k in slots:
+            setattr(self.ema, k, FlatStore(self.ema, S.compute_dtype))
+        self.ema.eval()
+        for p in self.ema.parameters():
+            p.requires_grad_(False)
+        self.decay = float(decay)
+        self.warmup = bool(warmup)
+        self.updates = 0
+        self._layout_key = self._mask_key = self._buf_key = None
+        self._mask = self._buf_table = None
+        self._buf_slots, self._buf_n = [], 0
+
+    @property
+    def module(self):
+        return self.ema
+
+    def decay_at(self, t):
+        """the decay of update number t (counted from 1)"""
+        return min(self.decay, (1 + t) / (10 + t)) if self.warmup else self.decay
+
+    def _ensure(self, src):
+        S = src.store
+        if S.P is None:
+            raise RuntimeError("FusedModelEma: run a forward of the model first (its flat parameter store is built lazily)")
+        E, dev = self.ema.store, S.P.device
+        if E.P is None or E.device != dev or not E.is_current():
+            if any(t.device != dev for t in self.ema.parameters()) or any(t.device != dev for t in self.ema.buffers()):
+                self.ema.to(dev)
+            E.ensure(dev)
+        key = (S.P.data_ptr(), E.P.data_ptr())
+        if self._layout_key != key:
+            if list(S.offsets.items()) != list(E.offsets.items()) or S.total != E.total:
+                raise RuntimeError("FusedModelEma: the model's flat store and the averaged model's are laid out differently (not the model this average was built from?)")
+            # the two module trees are walked HERE, not per update (0.2 ms of host time for pvlt_tiny), for the SLOTS that hold their buffers -- (the module's
+            # `_buffers` dict, name) -- so that each update reads the tensor a slot holds now: a buffer re-registered as a new tensor, or one whose storage moved,
+            # changes the key below.  Whatever replaces every tensor of a module (.to(), .cuda(), .float()) re-materialises its store and comes through this branch.
+            slots = lambda mod: [(m._buffers, k) for m in mod.modules() for k, b in m._buffers.items() if b is not None]
+            self._buf_slots = list(zip(slots(src), slots(self.ema)))
+            if any(ks != ke for (_, ks), (_, ke) in self._buf_slots) or len(slots(src)) != len(slots(self.ema)):
+                raise RuntimeError("FusedModelEma: the model's buffers and the averaged model's do not pair up by name")
+            self._buf_key = None
+            self._layout_key = key
+        key = (S.P.data_ptr(), E.P.data_ptr(), tuple(p.requires_grad for p in S._plist))
+        if self._mask_key != key:                # a store was re-materialised, or a parameter was frozen / un-frozen (as FusedAdamW's mask)
+            self._mask = None                    # nothing frozen: no mask, and the alignment gaps (zeros in both stores) average to zeros
+            if not all(key[2]):
+                mask = torch.zeros(S.total, dtype=torch.uint8)
+                for name, p in S.params.items():
+                    if not p.requires_grad:
+                        off, n, _ = S.offsets[name]
+                        mask[off:off + n] = ops.ADAMW_FROZEN
+                self._mask = mask.to(dev)
+            self._mask_key = key
+        pairs = [(ds[ks], de[ke]) for (ds, ks), (de, ke) in self._buf_slots]
+        key = tuple(t.data_ptr() for pair in pairs for t in pair)
+        if self._buf_key != key:
+            rows = []
+            for b, e in pairs:
+                if b.shape != e.shape or b.dtype != e.dtype or not (b.is_contiguous() and e.is_contiguous()):
+                    raise RuntimeError("FusedModelEma: the model's buffers and the averaged model's differ in shape, dtype or layout")
+                if b.dtype not in (torch.float32, torch.int64):
+                    raise RuntimeError(f"FusedModelEma: a {b.dtype} buffer (fp32 buffers are averaged, int64 ones copied)")
+                if b.numel():
+                    rows.append([ops.ptr(e), ops.ptr(b), b.numel(), 0 if b.dtype == torch.float32 else 1])
+            self._buf_n = len(rows)
+            self._buf_table = torch.tensor(rows, dtype=torch.int64).to(dev) if rows else None
+            self._buf_key = key
+        return S, E
+
+    @torch.no_grad()
+    def update(self, model):
+        """One launch over the parameters (+ one over the buffers, when the model has any) on the current stream, behind the optimizer step that was
+        enqueued before it; no host wait, nothing read from the device."""
+        S, E = self._ensure(_unwrap(model))
+        d = self.decay_at(self.updates + 1)
+        # Is the averaged model's bf16 copy current for its parameters as they stand BEFORE this launch?  Yes when its last refresh() cast (or accepted) it at this
+        # version, or when an earlier update declared it fresh at this version; no for a store that has just been materialised (C is uninitialised: refresh()
+        # makes the first cast) and after set() / load_state_dict() wrote the parameters.
+        ver = E.versions()
+        c_current = E.C is not None and ver in (E._cast_version, E._c_fresh_version)
+        ops.ema_update(E.P, S.P, E.C, S.total, d, 1.0 - d, self._mask)
+        if self._buf_n:
+            ops.ema_update_buffers(self._buf_table, self._buf_n, d, 1.0 - d)
+        self.updates += 1
+        # as after FusedAdamW.step: the W^T / permuted conv copies (and what the MIM decoder folds out of the BatchNorm buffers) are refreshed by the averaged
+        # model's next forward.  Its plain bf16 copy is declared current -- the forward then skips its cast -- only when this launch left it so: it wrote every
+        # element (no mask), or the elements the mask made it skip were current already.  Otherwise refresh() casts, as for any store.
+        E.force_dirty = True
+        E._c_fresh_version = E.versions() if E.C is not None and (self._mask is None or c_current) else None
+
+    @torch.no_grad()
+    def set(self, model):
+        """the average becomes a copy of `model`: one flat copy for the parameters, one copy per buffer"""
+        src = _unwrap(model)
+        if src.store.P is None:
+            self.ema.load_state_dict(src.state_dict())
+            return
+        S, E = self._ensure(src)
+        E.P.copy_(S.P)                            # (bumps P's version: the next forward re-casts and refreshes)
+        for b, e in zip(src.buffers(), self.ema.buffers()):
+            e.copy_(b)
+        E.force_dirty = True
+
+    def state_dict(self):
+        """The averaged model's state_dict -- what timm's get_state_dict(model_ema) stores; plus "_ema_updates", a key that the load hook of pvlt.PyramidVisionLanguageTransformer drops: the checkpoint loads into a plain model of that class, strict (any other
+        module wants the key deleted first)."""
+        sd = self.ema.state_dict()
+        sd["_ema_updates"] = self.updates
+        return sd
+
+    def load_state_dict(self, sd):
+        """Takes a checkpoint of state_dict() or any state_dict of the model (no "_ema_updates": `updates` stays as it is).  Works before the first
+        forward: the values then wait in the averaged model's parameters until its store is built."""
+        clean = type(sd)((k, v) for k, v in sd.items() if k != "_ema_updates") if isinstance(sd, dict) else sd
+        if hasattr(sd, "_metadata"):
+            clean._metadata = sd._metadata
+        self.ema.load_state_dict(clean)
+        self.ema.store.force_dirty = True
+        if "_ema_updates" in sd:
+            self.updates = int(sd["_ema_updates"])

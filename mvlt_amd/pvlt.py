@@ -218,6 +218,8 @@ class PyramidVisionLanguageTransformer(nn.Module):
     def _drop_legacy_keys(module, state_dict, prefix, *args):
         # transformers==4.10.2 checkpoints carry a persistent BertEmbeddings.position_ids buffer
         state_dict.pop(prefix + "text_embeddings.position_ids", None)
+        if not prefix:
+            state_dict.pop("_ema_updates", None)            # the one extra key of an optim.FusedModelEma checkpoint: it loads into a plain model
 
     def _operand_lists(self):
         transposed, conv_perm = [], []
