@@ -1,0 +1,64 @@
+/* mvlt_hip_plan.h -- what mvlt_gemm_nt / mvlt_gemm_tn WOULD launch for an argument struct, without launching it: entry points of libmvlt_hip.so added
+ * beside the C ABI of mvlt_hip.h (version 8) and the additions of mvlt_hip_ext.h and mvlt_hip_ema.h, whose lists of prototypes and versions stay as they are.
+ *
+ * The two GEMM entry points are "plan, then launch": the plan -- argument checks, choice of kernel instantiation, launch geometry, trailing kernel
+ * arguments, partial-tile bookkeeping -- is a pure host function (mvlt_amd/csrc/gemm_plan.h: no HIP call, no global state), and the entry points below
+ * hand it out.  They touch no device: they run on a machine without a GPU, and tests/test_gemm_plan_cpu.py pins them against recorded launches.
+ * A binding compares mvlt_plan_version() with the MVLT_PLAN_VERSION it was written against (mvlt_amd/_lib.py PLAN_VERSION) before it calls anything here.
+ */
+#ifndef MVLT_HIP_PLAN_H
+#define MVLT_HIP_PLAN_H
+#include <stddef.h>
+#include "mvlt_hip.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Version of this header: bumped whenever a signature or the struct below changes.
+ *   1: mvlt_gemm_plan, mvlt_gemm_nt_plan(), mvlt_gemm_tn_plan(), mvlt_gemm_plan_name(), mvlt_gemm_plan_sizeof() */
+#define MVLT_PLAN_VERSION 1
+int mvlt_plan_version(void);
+
+/* kernel families of mvlt_amd/csrc/gemm.hip; tp[] holds the template arguments of the instantiation in the order the kernel declares them
+ * (bool as 0 / 1, an element type as its dtype code) */
+#define MVLT_GEMM_NONE 0        /* M == 0: nothing to launch */
+#define MVLT_GEMM_NT_F32 1      /* gemm_nt_kernel<float, BN>                           tp = {BN} */
+#define MVLT_GEMM_NT_DMA 2      /* gemm_nt_dma_kernel<BN, AMODE, EPI, BK, 128>         tp = {BN, AMODE, EPI, BK} */
+#define MVLT_GEMM_NT_P8 3       /* gemm_nt_p8_kernel<EPI, HM, HN0, HN1, RAG>           tp = {EPI, HM, HN0, HN1, RAG} */
+#define MVLT_GEMM_NT_CONV3 4    /* conv3_nt_kernel<W, BN, EPI>                         tp = {W, BN, EPI} */
+#define MVLT_GEMM_TN_PLAIN 5    /* gemm_tn_kernel<T, BN>                               tp = {dtype, BN} */
+#define MVLT_GEMM_TN_DMA 6      /* gemm_tn_dma_kernel<BMT, BN, BMODE, NS, DG>          tp = {BMT, BN, BMODE, NS, DG} */
+#define MVLT_GEMM_TN_P8 7       /* gemm_tn_p8_kernel<HM, HN0, HN1, TRANS, RAG1, SWAP>  tp = {HM, HN0, HN1, TRANS, RAG1, SWAP} */
+#define MVLT_GEMM_TN_CONV3 8    /* conv3_wgrad_kernel<W>                               tp = {W} */
+
+typedef struct mvlt_gemm_plan {
+  int family;                /* MVLT_GEMM_* */
+  int tp[6];
+  int grid[3];
+  int block;
+  int lds;                   /* dynamic LDS bytes */
+  /* the scalar kernel arguments behind the argument struct, as each family uses them (0 where it has none) */
+  int ns_flags;              /* NT_DMA: ring depth | 0x100 (early slot release) */
+  int nbuf;                  /* NT_F32 */
+  int per_split;             /* TN_PLAIN / TN_DMA: m_per_split (rows);  TN_P8: kt_per (64-row k-tiles);  TN_CONV3: tiles_per_split */
+  int t1, t2;                /* TN_DMA / TN_P8: output tiles along N1 / N2 of the kernel's operands;  TN_CONV3: n_o, n_c (64-wide blocks of outputs / input channels) */
+  int splits;                /* TN: m-splits */
+  int swap_operands;         /* TN_P8 on 192 x 320 tiles when the 320-multiple side is the caller's N1: the kernel gets A and B (with their strides, sizes and column sums) exchanged */
+  int fold;                  /* 1: the splits store bf16 partial tiles to the caller's scratch and an ordered fold adds them to C */
+  int fold_grid;             /* workgroups of that fold (256 threads each) */
+  long partials_need;        /* bytes of mvlt_gemm_tn_args.partials this launch takes; 0 = atomics or a plain store */
+} mvlt_gemm_plan;
+
+/* Argument checks + choice, exactly what mvlt_gemm_nt / mvlt_gemm_tn do before they launch: same return codes, same mvlt_last_error() texts.  Pointers are
+ * looked at (null or not, low four address bits, equality), never followed. */
+int mvlt_gemm_nt_plan(const mvlt_gemm_nt_args* args, mvlt_gemm_plan* plan);
+int mvlt_gemm_tn_plan(const mvlt_gemm_tn_args* args, mvlt_gemm_plan* plan);
+/* the planned kernel's name as mvlt_last_kernel() prints it, without return type, namespace and parameter list: "gemm_nt_p8_kernel<1, 3, 3, 2, true>"
+ * ("" for MVLT_GEMM_NONE).  Returns the length written, <0 when buf is too small or the family unknown. */
+int mvlt_gemm_plan_name(const mvlt_gemm_plan* plan, char* buf, size_t n);
+int mvlt_gemm_plan_sizeof(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,4 +1,4 @@
-"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h and include/mvlt_hip_ema.h).
+"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h, include/mvlt_hip_ema.h and include/mvlt_hip_plan.h).
 
 The product path has NO fallback: importing this module without the built library, or calling an op without a
 GPU, raises.  torch is used only for device memory and streams.
@@ -226,6 +226,33 @@ for _name, (_res, _args) in EMA_PROTOTYPES.items():
 EMA_VERSION = 1          # include/mvlt_hip_ema.h MVLT_EMA_VERSION this binding was written against
 if lib.mvlt_ema_version() != EMA_VERSION:
     raise ImportError(f"EMA entry points mismatch: {LIB_PATH} is version {lib.mvlt_ema_version()}, the binding is version {EMA_VERSION} (stale build? run python -m mvlt_amd.build)")
+
+# The entry points of include/mvlt_hip_plan.h (what mvlt_gemm_nt / mvlt_gemm_tn would launch, without a device): a fourth table with its own struct,
+# bound and version-checked like the ones above (tests/test_gemm_plan_cpu.py compares both with that header).
+class GemmPlan(C.Structure):
+    _fields_ = [("family", c_int), ("tp", c_int * 6), ("grid", c_int * 3), ("block", c_int), ("lds", c_int),
+                ("ns_flags", c_int), ("nbuf", c_int), ("per_split", c_int), ("t1", c_int), ("t2", c_int), ("splits", c_int),
+                ("swap_operands", c_int), ("fold", c_int), ("fold_grid", c_int), ("partials_need", c_long)]
+
+
+PLAN_STRUCTS = (("mvlt_gemm_plan", GemmPlan),)
+PLAN_PROTOTYPES = {
+    "mvlt_plan_version": (_i, []),
+    "mvlt_gemm_nt_plan": (_i, [C.POINTER(GemmNTArgs), C.POINTER(GemmPlan)]),
+    "mvlt_gemm_tn_plan": (_i, [C.POINTER(GemmTNArgs), C.POINTER(GemmPlan)]),
+    "mvlt_gemm_plan_name": (_i, [C.POINTER(GemmPlan), _str, C.c_size_t]),
+    "mvlt_gemm_plan_sizeof": (_i, []),
+}
+for _name, (_res, _args) in PLAN_PROTOTYPES.items():
+    if not hasattr(lib, _name):
+        raise ImportError(f"{LIB_PATH} does not export {_name} (include/mvlt_hip_plan.h): stale build? run python -m mvlt_amd.build")
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
+PLAN_VERSION = 1         # include/mvlt_hip_plan.h MVLT_PLAN_VERSION this binding was written against
+if lib.mvlt_plan_version() != PLAN_VERSION or lib.mvlt_gemm_plan_sizeof() != C.sizeof(GemmPlan):
+    raise ImportError(f"GEMM plan entry points mismatch: {LIB_PATH} is version {lib.mvlt_plan_version()} with a {lib.mvlt_gemm_plan_sizeof()}-byte mvlt_gemm_plan, the binding is "
+                      f"version {PLAN_VERSION} with {C.sizeof(GemmPlan)} bytes (stale build? run python -m mvlt_amd.build)")
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 

@@ -15,12 +15,10 @@
 #endif                       // 128-wide kernels (four workgroups per CU hide the epilogue's VALU work); on the 8-wave kernels (two waves per SIMD, VALU-bound epilogue)
                              // GELU' is 10 instructions instead of 19.6 issue units: stage-4 GELU' dgrad 179 -> 157 us, stage-3 204 -> 181 us (same-box A/B, round 4)
 #include "common.h"
+#include "gemm_plan.h"
 #include <type_traits>
 #include <map>
 #include <mutex>
-#ifndef MVLT_NT_EARLY_DEFAULT
-#define MVLT_NT_EARLY_DEFAULT 0x100  // early slot release in the NT K-loop: logits GEMM 172 -> 163 us, step -0.16 ms (same-box A/B, MVLT_NT_EARLY=0 / 1)
-#endif
 #ifndef MVLT_ABL
 #define MVLT_ABL 0                   // timing ablations of the NT K-loop (wrong results): 1 no DMA, 2 no MFMA, 3 no fragment reads, 4 every DMA reads the zero page
 #endif
@@ -1704,30 +1702,6 @@ void fold_launch(const mvlt_gemm_tn_args& a, const bf16* part, int splits, hipSt
   f.used += ((long)splits * a.N1 * a.N2 * 2 + 255) & ~255L;
 }
 
-template <int W> int launch_conv3_wgrad(const mvlt_gemm_tn_args& a, hipStream_t s) {
-  constexpr int R = 64 / W, HR = (R + 2) * (W + 2), H_IT = (HR * 8 + NTHREADS - 1) / NTHREADS;
-  const size_t lds = (size_t)2 * (DmaTile<64>::BYTES + H_IT * NTHREADS * 16);
-  const int n_o = a.N1 / 64, n_c = a.b_map.c_seg / 64, ntiles = a.M / 64;
-  // every split flushes its whole 64 x 576 block with fp32 atomics: at least 16 k-tiles of work per flush, about two workgroups per
-  // CU when the shape allows (262144 x 64 x 576: 640 splits of 7 tiles 108 us, 256 splits of 16 tiles measured below)
-  constexpr int min_tiles = 16;
-  int splits = (512 + n_o * n_c - 1) / (n_o * n_c);
-  if (splits > ntiles / min_tiles) splits = ntiles / min_tiles;
-  if (splits < 1) splits = 1;
-  if (splits >= 8) splits = (splits + 4) / 8 * 8;
-  if (splits > ntiles) splits = ntiles;
-  const int tps = (ntiles + splits - 1) / splits;
-  splits = (ntiles + tps - 1) / tps;
-  dim3 grid((unsigned)((splits >= 8 ? 8 * ((splits + 7) / 8) : splits) * n_o * n_c)), block(NTHREADS);
-  mvlt_max_lds<(conv3_wgrad_kernel<W>)>();
-  // the caller's scratch takes the splits' blocks (bf16) and an ordered fold adds them to C: no atomics
-  bf16* const part = (a.partials && splits >= 4 && a.ldc % 4 == 0 && ((uintptr_t)a.C & 15) == 0 && lds >= (size_t)4 * 16 * (9 * 32 + 8) * 2)
-                         ? fold_acquire(a, (long)splits * a.N1 * a.N2 * 2, s) : nullptr;
-  MVLT_LAUNCH((conv3_wgrad_kernel<W>), grid, block, lds, s, a, tps, n_o, n_c, splits, part);
-  if (part) fold_launch(a, part, splits, s);
-  return mvlt_check_launch("mvlt_gemm_tn");
-}
-
 // ------------------------------------------------------------------------------------------------ NT, bf16, LDS-DMA
 // gemm_nt_kernel<bf16,BN> with the operand tiles filled by global_load_lds_dwordx4 instead of load -> VGPR ->
 // ds_write_b128 (LDS stores run at ~80 B/clk/CU, a third of the read rate, and were as expensive as the MFMAs).  The
@@ -2232,33 +2206,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_p8_kernel(mvlt_gemm_nt_args p)
   else nt_epilogue_w80<EPI, WMT, RAG>(p, acc, smem, m0, n0, wave, lane);
 }
 
-template <int EPI, int HM, int HN0, int HN1, bool RAG = false> void launch_nt_p8(const mvlt_gemm_nt_args& a, hipStream_t s) {
-  constexpr int BMT = 64 * HM, BNT = 64 * (HN0 + HN1);
-  constexpr int LDS_LOOP = 2 * (2 * (2 * HM * 16) + 64 * (HN0 + HN1)) * 128;
-  constexpr int LDS_EPI = 8 * 32 * (16 * (HN0 + HN1) + 4) * 4;
-  constexpr int LDS = LDS_LOOP > LDS_EPI ? LDS_LOOP : LDS_EPI;
-  mvlt_max_lds<(gemm_nt_p8_kernel<EPI, HM, HN0, HN1, RAG>)>();
-  const int tiles_m = (a.M + BMT - 1) / BMT, tiles_n = (a.N + BNT - 1) / BNT;
-  dim3 grid((unsigned)(8 * ((tiles_m + 7) / 8) * tiles_n)), block(512);
-  MVLT_LAUNCH((gemm_nt_p8_kernel<EPI, HM, HN0, HN1, RAG>), grid, block, LDS, s, a);
-}
-template <int HM, int HN0, int HN1> bool dispatch_nt_p8(const mvlt_gemm_nt_args& a, int epi, hipStream_t s) {
-  switch (epi) {
-    case 1: launch_nt_p8<1, HM, HN0, HN1>(a, s); return true;
-    case 2: launch_nt_p8<2, HM, HN0, HN1>(a, s); return true;
-    default: break;
-  }
-  if constexpr (HN0 + HN1 == 4) {
-    switch (epi) {
-      case 3: launch_nt_p8<3, HM, HN0, HN1>(a, s); return true;
-      case 4: launch_nt_p8<4, HM, HN0, HN1>(a, s); return true;
-      case 5: launch_nt_p8<5, HM, HN0, HN1>(a, s); return true;
-      default: break;
-    }
-  }
-  return false;
-}
-
 // ------------------------------------------------------------------------------------------------ TN (weight gradients), bf16, 8 waves, 8-phase loop
 // C[N1, N2] += A[M, N1]^T B[M, N2] on the schedule of gemm_nt_p8_kernel: the reduction runs over the ROWS of both operands (k-tile = 64 rows), the
 // operand tiles keep their natural [m][n] layout in LDS (LDS-DMA cannot transpose) and the MFMA fragments -- 8 consecutive m of one n per lane --
@@ -2624,54 +2571,6 @@ __global__ __launch_bounds__(256) void tn_fold_multi_kernel(FoldBatch b) {
   tn_fold_body(d.part, d.splits, d.N1, d.N2, d.C, d.ldc, (int)blockIdx.x - d.wg0);
 }
 
-template <int HM, int HN0, int HN1> int launch_tn_p8_partial(const mvlt_gemm_tn_args& a, hipStream_t s) {
-  constexpr int BM1 = 64 * HM, BN2 = 64 * (HN0 + HN1);
-  constexpr int LDS = 2 * 64 * 2 * (2 * (2 * HM * 16) + BN2);
-  mvlt_max_lds<(gemm_tn_p8_kernel<HM, HN0, HN1, true>)>();
-  const int t1 = a.N1 / BM1, t2 = a.N2 / BN2, nkt = a.M / 64;
-  int splits = 256 / (t1 * t2);                   // one workgroup per CU (the caller's scratch is sized for exactly this)
-  if (splits > nkt) splits = nkt;
-  const int kt_per = (nkt + splits - 1) / splits;
-  splits = (nkt + kt_per - 1) / kt_per;
-  bf16* const scratch = fold_acquire(a, (long)splits * a.N1 * a.N2 * 2, s);      // [splits][N1][N2] bf16 in the caller's scratch (mvlt_gemm_tn checked its size)
-  dim3 grid((unsigned)((splits >= 8 ? 8 * ((splits + 7) / 8) : splits) * t1 * t2)), block(512);
-  MVLT_LAUNCH((gemm_tn_p8_kernel<HM, HN0, HN1, true>), grid, block, LDS, s, a, kt_per, t1, t2, splits, scratch);
-  fold_launch(a, scratch, splits, s);
-  return mvlt_check_launch("mvlt_gemm_tn");
-}
-
-// 192 x 320 tiles (round 6): the caller's matrix is [N1][N2] with ONE side a multiple of 320 (taken as the kernel's column side, whole tiles) and the other covered by
-// ceil(. / 192) row tiles, the last one ragged.  swap: the 320 side is the caller's N1 -- operands exchanged, partial tiles stored transposed (in the caller's layout).
-template <bool SWAP> int launch_tn_p8_320(const mvlt_gemm_tn_args& a, hipStream_t s) {
-  constexpr int LDS = 2 * 64 * 2 * (2 * (2 * 3 * 16) + 320);
-  mvlt_gemm_tn_args k = a;
-  if (SWAP) {
-    k.A = a.B; k.B = a.A; k.lda = a.ldb; k.ldb = a.lda; k.N1 = a.N2; k.N2 = a.N1;
-    k.colsum_a = a.colsum_b; k.colsum_b = a.colsum_a;
-  }
-  const int t1 = (k.N1 + 191) / 192, t2 = k.N2 / 320, nkt = k.M / 64;
-  // all tiles of an m-split run on ONE XCD (32 CUs, one workgroup each): whole splits per XCD, the same number on each -- 7 tiles: 4 splits per XCD = 32 splits = 224
-  // workgroups (36 splits = 252 workgroups put 35 on four of the XCDs: a second round there, 184 us instead of the 128-wide kernel's 137)
-  int splits = (32 / (t1 * t2)) * 8;
-  if (splits < 8) splits = 256 / (t1 * t2);
-  if (splits > nkt) splits = nkt;
-  const int kt_per = (nkt + splits - 1) / splits;
-  splits = (nkt + kt_per - 1) / kt_per;
-  bf16* const scratch = fold_acquire(a, (long)splits * a.N1 * a.N2 * 2, s);      // [splits][caller N1][caller N2] bf16
-  if (!scratch) return 1;                                                          // (does not fit: the caller falls through to the 128-wide kernel)
-  dim3 grid((unsigned)((splits >= 8 ? 8 * ((splits + 7) / 8) : splits) * t1 * t2)), block(512);
-  const bool rag = k.N1 % 192 != 0;
-  if (SWAP) {
-    if (rag) { mvlt_max_lds<(gemm_tn_p8_kernel<3, 3, 2, false, true, true>)>(); MVLT_LAUNCH((gemm_tn_p8_kernel<3, 3, 2, false, true, true>), grid, block, LDS, s, k, kt_per, t1, t2, splits, scratch); }
-    else { mvlt_max_lds<(gemm_tn_p8_kernel<3, 3, 2, false, false, true>)>(); MVLT_LAUNCH((gemm_tn_p8_kernel<3, 3, 2, false, false, true>), grid, block, LDS, s, k, kt_per, t1, t2, splits, scratch); }
-  } else {
-    if (rag) { mvlt_max_lds<(gemm_tn_p8_kernel<3, 3, 2, true, true, false>)>(); MVLT_LAUNCH((gemm_tn_p8_kernel<3, 3, 2, true, true, false>), grid, block, LDS, s, k, kt_per, t1, t2, splits, scratch); }
-    else { mvlt_max_lds<(gemm_tn_p8_kernel<3, 3, 2, true, false, false>)>(); MVLT_LAUNCH((gemm_tn_p8_kernel<3, 3, 2, true, false, false>), grid, block, LDS, s, k, kt_per, t1, t2, splits, scratch); }
-  }
-  fold_launch(a, scratch, splits, s);
-  return mvlt_check_launch("mvlt_gemm_tn");
-}
-
 // ------------------------------------------------------------------------------------------------ conv3x3 forward / dgrad, LDS halo
 // C[pixel][n] = sum over taps t and channels c of x[pixel + tap t][c] * B[n][t*cin + c]: the MIM decoder's conv3x3 (and its input
 // gradient, the same gather with flipped taps) as the NT GEMM with a_map mode 2.  In gemm_nt_dma_kernel every k-step fetches its own
@@ -2809,225 +2708,135 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_nt_kernel(mvlt_gemm_nt_args
   else nt_epilogue_lean<BN, EPI, TM_>(p, acc, smem, m0, n0, wave, lane);
 }
 
-template <int W, int BN, int EPI> void launch_conv3_nt(const mvlt_gemm_nt_args& a, hipStream_t s) {
-  constexpr int R = BM / W, HR = (R + 2) * (W + 2), H_IT = (HR * 8 + NTHREADS - 1) / NTHREADS;
-  size_t lds = (size_t)H_IT * NTHREADS * 16 + (size_t)2 * BN * ROW_BYTES;
-  const size_t stage = (size_t)4 * 32 * (BN / 2 + 4) * sizeof(float);
-  if (lds < stage) lds = stage;
-  const int tiles_m = a.M / BM, tiles_n = (a.N + BN - 1) / BN;
-  dim3 grid((unsigned)(8 * ((tiles_m + 7) / 8) * tiles_n)), block(NTHREADS);
-  mvlt_max_lds<(conv3_nt_kernel<W, BN, EPI>)>();
-  MVLT_LAUNCH((conv3_nt_kernel<W, BN, EPI>), grid, block, lds, s, a);
-}
-template <int W> bool dispatch_conv3_nt(const mvlt_gemm_nt_args& a, int epi, hipStream_t s) {
-  const bool wide = a.N % 192 == 0 && a.N % 128 != 0 && (epi == 1 || epi == 5) && a.c_map.mode == 0;
-  if (wide) { if (epi == 1) launch_conv3_nt<W, 192, 1>(a, s); else launch_conv3_nt<W, 192, 5>(a, s); return true; }
-  if (a.N <= 64) {
-    switch (epi) {
-      case 1: launch_conv3_nt<W, 64, 1>(a, s); return true;
-      case 2: launch_conv3_nt<W, 64, 2>(a, s); return true;
-      case 5: launch_conv3_nt<W, 64, 5>(a, s); return true;
-      default: return false;
-    }
-  }
-  switch (epi) {
-    case 1: launch_conv3_nt<W, 128, 1>(a, s); return true;
-    case 2: launch_conv3_nt<W, 128, 2>(a, s); return true;
-    case 5: launch_conv3_nt<W, 128, 5>(a, s); return true;
-    default: return false;
-  }
+// ------------------------------------------------------------------------------------------------ plan -> launch
+// What to launch is decided in gemm_plan.h; below, a plan's family and template arguments are mapped to the instantiation, nothing else.  Every instantiation of
+// this file's GEMM kernels is one entry of these lists (tests/test_gemm_plan_cpu.py reads them); a plan none of them matches is an error, never another kernel.
+static_assert(mvlt_plan::BM == BM && mvlt_plan::NTHREADS == NTHREADS && mvlt_plan::ROW_BYTES == ROW_BYTES && mvlt_plan::TBK == TBK &&
+              mvlt_plan::TN_ROWB_BF16 == TElem<bf16>::ROWB && mvlt_plan::TN_ROWB_F32 == TElem<float>::ROWB && mvlt_plan::TN_TILE64_BYTES == DmaTile<64>::BYTES,
+              "gemm_plan.h sizes the launches with its own copies of the kernels' constants");
+constexpr long tkey(int family, int a, int b = 0, int c = 0, int d = 0, int e = 0, int f = 0) { return ((((((long)family * 400 + a) * 400 + b) * 400 + c) * 400 + d) * 2 + e) * 2 + f; }
+// RAISE: the instantiation needs more than the default 64 KB of dynamic LDS
+#define MVLT_CASE(RAISE, KERNEL, KEY, ...)                                   \
+  case tkey KEY:                                                             \
+    if constexpr (RAISE) mvlt_max_lds<KERNEL>();                             \
+    MVLT_LAUNCH(KERNEL, grid, block, lds, s, __VA_ARGS__);                   \
+    return mvlt_check_launch(who);
+#define MVLT_PLAN_LAUNCH_HEAD                                                                                          \
+  const dim3 grid((unsigned)p.grid[0], (unsigned)p.grid[1], (unsigned)p.grid[2]), block((unsigned)p.block);            \
+  const size_t lds = (size_t)p.lds;                                                                                    \
+  const long key = tkey(p.family, p.tp[0], p.tp[1], p.tp[2], p.tp[3], p.tp[4], p.tp[5])
+int no_instantiation(const char* who, const mvlt_gemm_plan& p) {
+  char name[128] = "?";
+  plan_kernel_name(p, name, sizeof(name));
+  mvlt_set_error("%s: the plan names %s (family %d), which this library does not instantiate", who, name, p.family);
+  return MVLT_ERR_UNSUPPORTED;
 }
 
-int check_rowmap(const mvlt_rowmap& m, const char* who) {
-  if (m.mode == 0) {
-    MVLT_REQUIRE(m.rows_per_batch >= 0, "%s: rows_per_batch < 0", who);
-  } else if (m.mode == 1) {
-    MVLT_REQUIRE(m.r > 0 && m.w_in > 0 && m.tokens_in > 0 && m.hw_out > 0 && m.w_out > 0 && m.c_seg > 0 && m.c_seg % 16 == 0,
-                 "%s: bad patch map (c_seg must be a positive multiple of 16)", who);
-  } else if (m.mode == 2) {
-    MVLT_REQUIRE(m.r == 3 && m.w_in > 0 && m.h_in > 0 && m.tokens_in >= m.h_in * m.w_in && m.hw_out == m.h_in * m.w_in &&
-                 m.w_out == m.w_in && m.c_seg > 0 && m.c_seg % 8 == 0, "%s: bad 3x3 neighbourhood map", who);
-  } else {
-    MVLT_REQUIRE(false, "%s: unknown rowmap mode %d", who, m.mode);
+int launch_nt(const mvlt_gemm_plan& p, const mvlt_gemm_nt_args& a, hipStream_t s) {
+  const char* const who = "mvlt_gemm_nt";
+  MVLT_PLAN_LAUNCH_HEAD;
+#define NT_F32(BN_) MVLT_CASE(false, (gemm_nt_kernel<float, BN_>), (MVLT_GEMM_NT_F32, BN_), a, p.nbuf)
+#define NT_DMA(BN_, AM_, EPI_, BK_) MVLT_CASE(false, (gemm_nt_dma_kernel<BN_, AM_, EPI_, BK_>), (MVLT_GEMM_NT_DMA, BN_, AM_, EPI_, BK_), a, p.ns_flags)
+#define NT_DMA_EPIS(BN_, AM_) NT_DMA(BN_, AM_, 1, 64) NT_DMA(BN_, AM_, 2, 64) NT_DMA(BN_, AM_, 3, 64) NT_DMA(BN_, AM_, 4, 64) \
+                              NT_DMA(BN_, AM_, 5, 64) NT_DMA(BN_, AM_, 6, 64) NT_DMA(BN_, AM_, 7, 64) NT_DMA(BN_, AM_, 0, 64)
+#define NT_P8(EPI_, HM_, HN0_, HN1_, RAG_) MVLT_CASE(true, (gemm_nt_p8_kernel<EPI_, HM_, HN0_, HN1_, RAG_>), (MVLT_GEMM_NT_P8, EPI_, HM_, HN0_, HN1_, RAG_), a)
+#define NT_CONV3(W_, BN_, EPI_) MVLT_CASE(true, (conv3_nt_kernel<W_, BN_, EPI_>), (MVLT_GEMM_NT_CONV3, W_, BN_, EPI_), a)
+#define NT_CONV3_W(W_) NT_CONV3(W_, 192, 1) NT_CONV3(W_, 192, 5) NT_CONV3(W_, 64, 1) NT_CONV3(W_, 64, 2) NT_CONV3(W_, 64, 5) \
+                       NT_CONV3(W_, 128, 1) NT_CONV3(W_, 128, 2) NT_CONV3(W_, 128, 5)
+  switch (key) {        // (in the order the instantiations have always been emitted in: the code object stays byte for byte what it was)
+    NT_DMA(64, 0, 8, 64) NT_DMA(128, 0, 8, 64)
+    NT_CONV3_W(32) NT_CONV3_W(16) NT_CONV3_W(64)
+    NT_P8(1, 4, 2, 2, true) NT_P8(1, 3, 3, 2, true) NT_P8(2, 3, 3, 2, true) NT_P8(1, 3, 3, 2, false) NT_P8(2, 3, 3, 2, false)
+    NT_P8(1, 4, 2, 2, false) NT_P8(2, 4, 2, 2, false) NT_P8(3, 4, 2, 2, false) NT_P8(4, 4, 2, 2, false) NT_P8(5, 4, 2, 2, false)
+    NT_P8(1, 3, 2, 2, false) NT_P8(2, 3, 2, 2, false) NT_P8(3, 3, 2, 2, false) NT_P8(4, 3, 2, 2, false) NT_P8(5, 3, 2, 2, false)
+    NT_DMA(192, 0, 1, 64) NT_DMA(192, 0, 5, 64) NT_DMA(192, 2, 1, 64) NT_DMA(192, 2, 5, 64)
+    NT_DMA_EPIS(64, 0) NT_DMA_EPIS(64, 1) NT_DMA_EPIS(64, 2)
+    NT_DMA(128, 0, 3, 32) NT_DMA(128, 0, 4, 32)
+    NT_DMA_EPIS(128, 0) NT_DMA_EPIS(128, 1) NT_DMA_EPIS(128, 2)
+    NT_F32(64) NT_F32(128)
   }
-  return MVLT_OK;
+#undef NT_F32
+#undef NT_DMA
+#undef NT_DMA_EPIS
+#undef NT_P8
+#undef NT_CONV3
+#undef NT_CONV3_W
+  return no_instantiation(who, p);
 }
+
+int launch_tn(const mvlt_gemm_plan& p, const mvlt_gemm_tn_args& a, hipStream_t s) {
+  const char* const who = "mvlt_gemm_tn";
+  MVLT_PLAN_LAUNCH_HEAD;
+  mvlt_gemm_tn_args k = a;                    // what the kernel sees: the caller's operands, or (192 x 320 tiles with the 320 side on N1) exchanged
+  if (p.swap_operands) {
+    k.A = a.B; k.B = a.A; k.lda = a.ldb; k.ldb = a.lda; k.N1 = a.N2; k.N2 = a.N1;
+    k.colsum_a = a.colsum_b; k.colsum_b = a.colsum_a;
+  }
+  // [splits][caller N1][caller N2] bf16 in the caller's scratch; the plan has checked everything the bookkeeping can refuse on
+  bf16* const part = p.fold ? fold_acquire(a, p.partials_need, s) : nullptr;
+  if (p.fold && !part) { mvlt_set_error("%s: the planned %ld bytes of partial tiles do not fit the scratch", who, p.partials_need); return MVLT_ERR_ARG; }
+#define TN_PLAIN(T_, DT_, BN_) MVLT_CASE(false, (gemm_tn_kernel<T_, BN_>), (MVLT_GEMM_TN_PLAIN, DT_, BN_), k, p.per_split)
+#define TN_DMA(BMT_, BN_, BMODE_, NS_, DG_) \
+  MVLT_CASE(DG_, (gemm_tn_dma_kernel<BMT_, BN_, BMODE_, NS_, DG_>), (MVLT_GEMM_TN_DMA, BMT_, BN_, BMODE_, NS_, DG_), k, p.per_split, p.t1, p.t2, p.splits, part)
+#define TN_DMA_MODES(BMT_, BN_, NS_) TN_DMA(BMT_, BN_, 3, NS_, false) TN_DMA(BMT_, BN_, 0, NS_, false) TN_DMA(BMT_, BN_, 1, NS_, false) TN_DMA(BMT_, BN_, 2, NS_, false)
+#define TN_P8(HM_, HN0_, HN1_, TRANS_, RAG1_, SWAP_) \
+  MVLT_CASE(true, (gemm_tn_p8_kernel<HM_, HN0_, HN1_, TRANS_, RAG1_, SWAP_>), (MVLT_GEMM_TN_P8, HM_, HN0_, HN1_, TRANS_, RAG1_, SWAP_), k, p.per_split, p.t1, p.t2, p.splits, part)
+#define TN_CONV3(W_) MVLT_CASE(true, (conv3_wgrad_kernel<W_>), (MVLT_GEMM_TN_CONV3, W_), k, p.per_split, p.t1, p.t2, p.splits, part)
+  auto launch = [&]() -> int {
+    switch (key) {
+      TN_CONV3(64) TN_CONV3(32) TN_CONV3(16) TN_CONV3(8)
+      TN_P8(4, 2, 2, true, false, false)
+      TN_P8(3, 3, 2, false, true, true) TN_P8(3, 3, 2, false, false, true) TN_P8(3, 3, 2, true, true, false) TN_P8(3, 3, 2, true, false, false)
+      TN_DMA(64, 64, 3, 4, true) TN_DMA(128, 128, 3, 2, true)
+      TN_DMA_MODES(128, 128, 2) TN_DMA_MODES(128, 64, 3) TN_DMA_MODES(64, 128, 3) TN_DMA_MODES(64, 64, 4)
+      TN_PLAIN(bf16, 0, 64) TN_PLAIN(bf16, 0, 128) TN_PLAIN(float, 1, 64) TN_PLAIN(float, 1, 128)
+    }
+    return no_instantiation(who, p);
+  };
+#undef TN_PLAIN
+#undef TN_DMA
+#undef TN_DMA_MODES
+#undef TN_P8
+#undef TN_CONV3
+  // the fold (a launch, or an entry of the pending table) follows its producer on the same stream
+  const int e = launch();
+  if (e != MVLT_OK || !p.fold) return e;
+  fold_launch(a, part, p.splits, s);
+  return mvlt_check_launch(who);
+}
+#undef MVLT_CASE
+#undef MVLT_PLAN_LAUNCH_HEAD
 
 }  // namespace
 
 extern "C" int mvlt_gemm_nt(const mvlt_gemm_nt_args* a, void* stream) {
-  MVLT_REQUIRE(a && a->A && a->B && a->C, "mvlt_gemm_nt: null operand");
-  MVLT_REQUIRE(a->M >= 0 && a->N > 0 && a->K > 0, "mvlt_gemm_nt: bad shape M=%d N=%d K=%d", a->M, a->N, a->K);
-  MVLT_REQUIRE(a->dtype == 0 || a->dtype == 1, "mvlt_gemm_nt: dtype must be 0 (bf16) or 1 (fp32)");
-  const int pc = a->dtype == 0 ? 8 : 4;
-  MVLT_REQUIRE(a->K % pc == 0 && a->lda % pc == 0 && a->ldb % pc == 0, "mvlt_gemm_nt: K/lda/ldb must be multiples of %d elements (16 B)", pc);
-  MVLT_REQUIRE(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->B & 15) == 0, "mvlt_gemm_nt: A/B must be 16-byte aligned");
-  MVLT_REQUIRE(a->act >= 0 && a->act <= 2, "mvlt_gemm_nt: bad act");
-  MVLT_REQUIRE(a->act != 2 || a->H, "mvlt_gemm_nt: act=2 (gelu') needs H");
-  MVLT_REQUIRE(!a->row_scale || a->rows_per_scale > 0, "mvlt_gemm_nt: row_scale needs rows_per_scale");
-  MVLT_REQUIRE((a->col_sum == nullptr) == (a->col_sumsq == nullptr), "mvlt_gemm_nt: col_sum and col_sumsq come together");
-  MVLT_REQUIRE(a->split_k <= 1 || (a->dtype == 0 && a->out_dtype == 1 && a->act == 0 && !a->H && !a->R && !a->row_scale && !a->col_sum &&
-                                   a->c_map.mode == 0 && a->split_k <= 64),
-               "mvlt_gemm_nt: split_k needs bf16 operands, fp32 C (zeroed by the caller) and a plain epilogue (A may be gathered)");
-  MVLT_REQUIRE(a->col_copies >= 0, "mvlt_gemm_nt: col_copies < 0");
-  MVLT_REQUIRE(!a->r_fp32 || (a->R && a->R != a->C && a->dtype == 0 && a->out_dtype == 0 && a->act == 0 && !a->col_sum && !a->post_y && a->split_k <= 1 && a->c_map.mode == 0 &&
-                              a->N % 8 == 0 && a->ldc % 8 == 0 && (((uintptr_t)a->C | (uintptr_t)a->R) & 15) == 0 && a->M < (1 << 24)),
-               "mvlt_gemm_nt: r_fp32 (fp32 residual beside a bf16 C) exists in the residual epilogue of the bf16 LDS-DMA kernels only (plain c_map, N % 8 == 0, 16-byte aligned C / R)");
-  MVLT_REQUIRE(a->out_dtype >= 0 && a->out_dtype <= 2, "mvlt_gemm_nt: out_dtype is 0 (bf16), 1 (fp32) or 2 (fp16, with col_sum only)");
-  MVLT_REQUIRE(a->out_dtype != 2 || (a->dtype == 0 && a->col_sum && a->act == 0 && !a->R && !a->row_scale && a->split_k <= 1 && a->c_map.mode == 0 && a->N % 8 == 0 &&
-                                     a->ldc % 8 == 0 && ((uintptr_t)a->C & 15) == 0 && a->M < (1 << 24)),
-               "mvlt_gemm_nt: fp16 output exists in the column-statistics epilogue of the bf16 LDS-DMA kernels only (plain c_map, N % 8 == 0, 16-byte aligned C)");
-  if (int e = check_rowmap(a->a_map, "mvlt_gemm_nt a_map")) return e;
-  if (int e = check_rowmap(a->c_map, "mvlt_gemm_nt c_map")) return e;
-  MVLT_REQUIRE(a->a_map.mode == 0 || a->K == a->a_map.r * a->a_map.r * a->a_map.c_seg, "mvlt_gemm_nt: gather K != r*r*c_seg");
-  MVLT_REQUIRE(a->c_map.mode == 0 || a->N == a->c_map.r * a->c_map.r * a->c_map.c_seg, "mvlt_gemm_nt: scatter N != r*r*c_seg");
-  MVLT_REQUIRE(a->c_map.mode != 2, "mvlt_gemm_nt: the 3x3 map is a gather only (its dgrad is a gather with flipped taps)");
-  // EPI 8 (LayerNorm of the finished row) exists in the bf16 LDS-DMA kernel only: every other launch path refuses instead of skipping it silently
-  MVLT_REQUIRE(!a->post_y || (a->dtype == 0 && a->split_k <= 1),
-               "mvlt_gemm_nt: post_y needs the bf16 LDS-DMA path (no fp32 operands, no split_k)");
-  if (a->M == 0) return MVLT_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int tiles_m = (a->M + BM - 1) / BM;
-  const bool narrow = a->N <= 64;
-  const int bn = narrow ? 64 : 128;
-  const int tiles_n = (a->N + bn - 1) / bn;
-  const int bk = a->dtype == 0 ? 64 : 32;
-  const int nbuf = a->K <= bk ? 1 : 2;
-  size_t lds = (size_t)nbuf * (BM + bn) * ROW_BYTES;
-  const size_t stage = (size_t)4 * 32 * (bn / 2 + 4) * sizeof(float);      // epilogue staging (4 waves x 32 rows)
-  if (lds < stage) lds = stage;
-  dim3 grid((unsigned)(8 * ((tiles_m + 7) / 8) * tiles_n), (unsigned)(a->split_k > 1 ? a->split_k : 1)), block(NTHREADS);
-  if (a->dtype == 0) {
-    const int nk = ((a->K + 63) / 64 + (a->split_k > 1 ? a->split_k : 1) - 1) / (a->split_k > 1 ? a->split_k : 1);
-    // compile-time epilogue variant (see nt_epilogue_lean); 0 = generic
-    int epi = 0;
-    // (N % 8 != 0 -- the 30522-word MLM logits -- takes the plain lean epilogue too: its last chunk of a row is stored column by column)
-    const bool plain_epi = a->act == 0 && !a->R && !a->row_scale && !a->col_sum && !a->H && a->c_map.mode == 0;
-    const bool lean_ok = (a->c_map.mode == 0 || (a->c_map.mode == 1 && a->c_map.c_seg % 8 == 0)) && a->split_k <= 1 && (a->N % 8 == 0 || plain_epi) && a->ldc % 8 == 0 && ((uintptr_t)a->C & 15) == 0 &&
-                         (!a->R || ((uintptr_t)a->R & 15) == 0) && (!a->H || ((uintptr_t)a->H & 15) == 0) && a->M < (1 << 24);
-    if (lean_ok && a->c_map.mode == 1) {
-      if (a->act == 0 && !a->col_sum && !a->R && !a->row_scale) epi = 6;
-      else if (a->act == 0 && !a->col_sum && a->R) epi = 7;
-    } else if (lean_ok) {
-      if (a->act == 1 && !a->R && !a->row_scale && !a->col_sum && a->out_dtype == 0) epi = 3;
-      else if (a->act == 2 && !a->R && !a->row_scale && !a->col_sum && a->out_dtype == 0) epi = 4;
-      else if (a->act == 0 && a->R && !a->col_sum) epi = 2;
-      else if (a->act == 0 && !a->R && !a->row_scale && a->col_sum) epi = 5;
-      else if (a->act == 0 && !a->R && !a->row_scale && !a->col_sum) epi = 1;
-    }
-    // ring depth: 2 stages (64 KB, two workgroups per CU).  A single stage at four workgroups per CU was tried: same time in
-    // the step, and its extra in-loop issue path cost 34 VGPRs (a wave per SIMD on the K <= 64 launches)
-    // The GELU epilogue (EPI 3) on the short-K fc1 GEMMs is epilogue-bound: 32-wide K stages halve the ring (32 KB) so a third
-    // workgroup fits per CU and covers it (98304x1280x320: 240 -> 220 us, 49152x2048x512: 234 -> 201 us).  Long K loses to the
-    // doubled barrier count (K = 2048: 103 -> 125 us), other epilogues are neutral; EPI 4 prefers its two-half H prefetch,
-    // whose registers allow two workgroups per CU either way (220 / 213 us against 227 / 217 us).
-    const int bkd = (!narrow && a->a_map.mode == 0 && (epi == 3 || epi == 4) && a->K <= 512) ? 32 : 64;
-    const int nkd = bkd == 32 ? (a->K + 31) / 32 : nk;
-    int ns = nkd < 2 ? nkd : 2;
-    size_t lds2 = (size_t)ns * (BM + bn) * (bkd * 2);
-    if (lds2 < stage) lds2 = stage;
-    const int ns_lds = ns;
-    if (nkd >= 2) ns |= MVLT_NT_EARLY_DEFAULT;                // (a single k-step has nothing to refill)
-    if (a->post_y) {                            // EPI 8: attn.proj + residual + Block.norm2 (whole rows in one tile)
-      MVLT_REQUIRE(epi == 2 && a->N == bn && a->a_map.mode == 0 && a->c_map.mode == 0 && a->c_map.rows_per_batch == 0 && a->post_gamma && a->post_beta &&
-                   a->post_mean && a->post_rstd && a->post_ld % 8 == 0 && ((uintptr_t)a->post_y & 15) == 0 && ((uintptr_t)a->post_gamma & 15) == 0,
-                   "mvlt_gemm_nt: post_y needs bf16 operands, a residual (R), N == 64 or 128, identity row maps, 16-byte aligned outputs");
-      if (lds2 < stage + 2048) lds2 = stage + 2048;
-      if (narrow) MVLT_LAUNCH((gemm_nt_dma_kernel<64, 0, 8, 64>), grid, block, lds2, s, *a, ns);
-      else MVLT_LAUNCH((gemm_nt_dma_kernel<128, 0, 8, 64>), grid, block, lds2, s, *a, ns);
-      return mvlt_check_launch("mvlt_gemm_nt");
-    }
-#define MVLT_NT_LAUNCH_E(BN_, AM_, BK_)                                                                                 \
-  do {                                                                                                               \
-    switch (epi) {                                                                                                   \
-      case 1: MVLT_LAUNCH((gemm_nt_dma_kernel<BN_, AM_, 1, BK_>), grid, block, lds2, s, *a, ns); break;            \
-      case 2: MVLT_LAUNCH((gemm_nt_dma_kernel<BN_, AM_, 2, BK_>), grid, block, lds2, s, *a, ns); break;            \
-      case 3: MVLT_LAUNCH((gemm_nt_dma_kernel<BN_, AM_, 3, BK_>), grid, block, lds2, s, *a, ns); break;            \
-      case 4: MVLT_LAUNCH((gemm_nt_dma_kernel<BN_, AM_, 4, BK_>), grid, block, lds2, s, *a, ns); break;            \
-      case 5: MVLT_LAUNCH((gemm_nt_dma_kernel<BN_, AM_, 5, BK_>), grid, block, lds2, s, *a, ns); break;            \
-      case 6: MVLT_LAUNCH((gemm_nt_dma_kernel<BN_, AM_, 6, BK_>), grid, block, lds2, s, *a, ns); break;            \
-      case 7: MVLT_LAUNCH((gemm_nt_dma_kernel<BN_, AM_, 7, BK_>), grid, block, lds2, s, *a, ns); break;            \
-      default: MVLT_LAUNCH((gemm_nt_dma_kernel<BN_, AM_, 0, BK_>), grid, block, lds2, s, *a, ns);                  \
-    }                                                                                                                \
-  } while (0)
-#define MVLT_NT_LAUNCH(BN_, BK_)                                                                                     \
-  do {                                                                                                               \
-    if (a->a_map.mode == 0) MVLT_NT_LAUNCH_E(BN_, 0, BK_);                                                           \
-    else if (a->a_map.mode == 1) MVLT_NT_LAUNCH_E(BN_, 1, BK_);                                                      \
-    else MVLT_NT_LAUNCH_E(BN_, 2, BK_);                                                                              \
-  } while (0)
-    // conv3x3 (a_map mode 2) on an LDS-resident, channel-sliced halo: grids of width 16 / 32 / 64, whole 128-pixel tiles inside one
-    // image, 64-multiples of gathered channels, lean epilogue, identity or batch-strided output rows
-    if (a->a_map.mode == 2 && (epi == 1 || epi == 2 || epi == 5) && a->split_k <= 1 && a->a_map.c_seg % 64 == 0 && a->c_map.mode == 0 &&
-        (a->a_map.w_in == 16 || a->a_map.w_in == 32 || a->a_map.w_in == 64) && (a->a_map.h_in * a->a_map.w_in) % BM == 0 && a->M % BM == 0 &&
-        a->M % (a->a_map.h_in * a->a_map.w_in) == 0 && a->a_map.hw_out == a->a_map.h_in * a->a_map.w_in && a->a_map.w_out == a->a_map.w_in &&
-        a->K == 9 * a->a_map.c_seg && a->lda >= a->a_map.c_seg && a->ldb >= a->K) {
-      bool done = a->a_map.w_in == 32 ? dispatch_conv3_nt<32>(*a, epi, s) : a->a_map.w_in == 16 ? dispatch_conv3_nt<16>(*a, epi, s) : dispatch_conv3_nt<64>(*a, epi, s);
-      if (done) return mvlt_check_launch("mvlt_gemm_nt");
-    }
-    // 8-wave kernels with the 8-phase K-loop (gemm_nt_p8_kernel) for the MFMA-bound shapes of the stage 3-4 MLPs: one workgroup per CU, so the
-    // tile height is chosen by whole rounds of 256 CUs (rows x rounds = time): 256 x 256, 192 x 256, or 192 x 320 for N % 320 == 0
-    if (a->a_map.mode == 0 && a->a_map.rows_per_batch == 0 && a->c_map.mode == 0 && epi >= 1 && epi <= 5 && a->K % 64 == 0 && a->K >= 128) {
-      auto cost = [&](int bm, int bn) -> long {                         // rows x rounds; 0 = shape does not fit
-        if (a->M % bm || a->N % bn) return 0;
-        const long tiles = (long)(a->M / bm) * (a->N / bn);
-        if (tiles < 192) return 0;
-        return ((tiles + 255) / 256) * (long)bm * bn;
-      };
-      const long c256 = cost(256, 256), c192 = cost(192, 256);
-      // (192 x 320 with the fp32 residual epilogue pays from K = 640 on: 98304 x 320 x 320 + R 93 us against 73 us on the 128-wide kernel, K = 1280 138 against 155)
-      const long c320 = (a->N % 256 != 0 && (epi == 1 || (epi == 2 && a->K >= 640))) ? cost(192, 320) : 0;
-      bool done = false;
-      // ragged M / N (the MLM logits, ~1500 x 30522 x 768, fp32 out): 256 x 256 tiles with the loader clamped at the last row and the checked epilogue
-      if (!c320 && !c256 && !c192 && epi == 1 && (a->M % 256 || a->N % 256)) {
-        const long tiles = (long)((a->M + 255) / 256) * ((a->N + 255) / 256);
-        // ... when the whole rounds of padded tiles are at least 85 % real work: 294912 x 128 would pad half of every 256-wide tile (36 -> 56 us), and
-        // 1558 selected rows make 7 x 120 tiles = 4 rounds where 1490 rows make 3 (the 128-wide kernel then wins)
-        const long rounds = (tiles + 255) / 256;
-        if (tiles >= 384 && (double)a->M * a->N >= 0.85 * (double)rounds * 256.0 * 65536.0) { launch_nt_p8<1, 4, 2, 2, true>(*a, s); done = true; }
-      }
-      // ragged M on the 192 x 320 tile (round 6; N % 320 == 0, same epilogue rules as the whole-tile form): pvlt_medium at 384 px runs its 18 stage-3 blocks at
-      // M = 45056 = 234.67 x 192 rows -- 235 tiles = ONE round at 92 % -- and took the 128-wide kernels for every N = 320 product (fc2 76 us, fc1 input gradient 66 us,
-      // q / proj 27 us: profiles/r06_medium384_gemm_shapes.txt); taken when the whole rounds of padded tiles are >= 85 % real work
-      if (!done && !c320 && !c256 && !c192 && a->N % 320 == 0 && a->N % 256 != 0 && a->M % 192 != 0 && (epi == 1 || (epi == 2 && a->K >= 640))) {
-        const long tiles = (long)((a->M + 191) / 192) * (a->N / 320);
-        const long rounds = (tiles + 255) / 256;
-        if (tiles >= 192 && (double)a->M * a->N >= 0.85 * (double)rounds * 256.0 * 192.0 * 320.0) {
-          if (epi == 1) launch_nt_p8<1, 3, 3, 2, true>(*a, s);
-          else launch_nt_p8<2, 3, 3, 2, true>(*a, s);
-          done = true;
-        }
-      }
-      if (done) return mvlt_check_launch("mvlt_gemm_nt");
-      if (c320) done = dispatch_nt_p8<3, 3, 2>(*a, epi, s);
-      else if (c256 && (!c192 || c256 <= c192)) done = dispatch_nt_p8<4, 2, 2>(*a, epi, s);
-      else if (c192) done = dispatch_nt_p8<3, 2, 2>(*a, epi, s);
-      if (done) return mvlt_check_launch("mvlt_gemm_nt");
-    }
-    // N % 192 == 0 (the 192-channel convolutions): one 192-wide tile instead of 128 + a half-empty 128
-    const bool wide = !narrow && a->N % 192 == 0 && a->N % 128 != 0 && (epi == 1 || epi == 5) && a->c_map.mode == 0 && a->a_map.mode != 1 &&
-                      a->K >= 128;
-    if (wide) {
-      const int tn192 = a->N / 192;
-      dim3 grid192((unsigned)(8 * ((tiles_m + 7) / 8) * tn192), 1);
-      size_t lds3 = (size_t)ns_lds * (BM + 192) * ROW_BYTES;
-      const size_t stage192 = (size_t)4 * 32 * 100 * sizeof(float);
-      if (lds3 < stage192) lds3 = stage192;
-      if (a->a_map.mode == 0 && epi == 1) MVLT_LAUNCH((gemm_nt_dma_kernel<192, 0, 1, 64>), grid192, block, lds3, s, *a, ns);
-      else if (a->a_map.mode == 0) MVLT_LAUNCH((gemm_nt_dma_kernel<192, 0, 5, 64>), grid192, block, lds3, s, *a, ns);
-      else if (epi == 1) MVLT_LAUNCH((gemm_nt_dma_kernel<192, 2, 1, 64>), grid192, block, lds3, s, *a, ns);
-      else MVLT_LAUNCH((gemm_nt_dma_kernel<192, 2, 5, 64>), grid192, block, lds3, s, *a, ns);
-    } else if (narrow) MVLT_NT_LAUNCH(64, 64);
-    else if (bkd == 32 && epi == 3) MVLT_LAUNCH((gemm_nt_dma_kernel<128, 0, 3, 32>), grid, block, lds2, s, *a, ns);
-    else if (bkd == 32) MVLT_LAUNCH((gemm_nt_dma_kernel<128, 0, 4, 32>), grid, block, lds2, s, *a, ns);
-    else MVLT_NT_LAUNCH(128, 64);
-#undef MVLT_NT_LAUNCH_E
-#undef MVLT_NT_LAUNCH
-  } else {
-    if (narrow) MVLT_LAUNCH((gemm_nt_kernel<float, 64>), grid, block, lds, s, *a, nbuf);
-    else MVLT_LAUNCH((gemm_nt_kernel<float, 128>), grid, block, lds, s, *a, nbuf);
-  }
-  return mvlt_check_launch("mvlt_gemm_nt");
+  mvlt_gemm_plan p;
+  MVLT_REQUIRE(a, "mvlt_gemm_nt: null operand");
+  if (int e = plan_gemm_nt(*a, p)) return e;
+  return p.family == MVLT_GEMM_NONE ? MVLT_OK : launch_nt(p, *a, (hipStream_t)stream);
+}
+
+extern "C" int mvlt_gemm_tn(const mvlt_gemm_tn_args* a, void* stream) {
+  mvlt_gemm_plan p;
+  MVLT_REQUIRE(a, "mvlt_gemm_tn: null operand");
+  if (int e = plan_gemm_tn(*a, p)) return e;
+  return p.family == MVLT_GEMM_NONE ? MVLT_OK : launch_tn(p, *a, (hipStream_t)stream);
+}
+
+// the plan without the launch (include/mvlt_hip_plan.h): no device is touched
+extern "C" int mvlt_plan_version(void) { return MVLT_PLAN_VERSION; }
+extern "C" int mvlt_gemm_plan_sizeof(void) { return (int)sizeof(mvlt_gemm_plan); }
+extern "C" int mvlt_gemm_nt_plan(const mvlt_gemm_nt_args* a, mvlt_gemm_plan* plan) {
+  MVLT_REQUIRE(a && plan, "mvlt_gemm_nt_plan: null argument");
+  return plan_gemm_nt(*a, *plan);
+}
+extern "C" int mvlt_gemm_tn_plan(const mvlt_gemm_tn_args* a, mvlt_gemm_plan* plan) {
+  MVLT_REQUIRE(a && plan, "mvlt_gemm_tn_plan: null argument");
+  return plan_gemm_tn(*a, *plan);
+}
+extern "C" int mvlt_gemm_plan_name(const mvlt_gemm_plan* plan, char* buf, size_t n) {
+  MVLT_REQUIRE(plan && buf && n > 0, "mvlt_gemm_plan_name: null argument");
+  return plan_kernel_name(*plan, buf, n);
 }
 
 bf16* mvlt_fold_acquire_ext(const mvlt_gemm_tn_args& a, long need, hipStream_t s, int descriptors) { return fold_acquire(a, need, s, descriptors); }
@@ -3049,167 +2858,3 @@ extern "C" int mvlt_tn_fold_flush(const void* partials, void* stream) {
   return mvlt_check_launch("mvlt_tn_fold_flush");
 }
 
-extern "C" int mvlt_gemm_tn(const mvlt_gemm_tn_args* a, void* stream) {
-  MVLT_REQUIRE(a && a->A && a->B && a->C, "mvlt_gemm_tn: null operand");
-  MVLT_REQUIRE(a->M >= 0 && a->N1 > 0 && a->N2 > 0, "mvlt_gemm_tn: bad shape");
-  MVLT_REQUIRE(a->dtype == 0 || a->dtype == 1, "mvlt_gemm_tn: dtype must be 0 (bf16) or 1 (fp32)");
-  const int pc = a->dtype == 0 ? 8 : 4;
-  // N1/N2 may be ragged (30522 vocabulary rows) as long as the padded row (lda/ldb) covers the last 16-B chunk
-  MVLT_REQUIRE(a->lda % pc == 0 && a->ldb % pc == 0, "mvlt_gemm_tn: lda/ldb must be multiples of %d elements (16 B)", pc);
-  MVLT_REQUIRE(a->lda >= (a->N1 + pc - 1) / pc * pc, "mvlt_gemm_tn: lda must cover N1 rounded up to %d", pc);
-  MVLT_REQUIRE(a->b_map.mode != 0 || a->ldb >= (a->N2 + pc - 1) / pc * pc, "mvlt_gemm_tn: ldb must cover N2 rounded up to %d", pc);
-  MVLT_REQUIRE(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->B & 15) == 0, "mvlt_gemm_tn: A/B must be 16-byte aligned");
-  if (int e = check_rowmap(a->a_map, "mvlt_gemm_tn a_map")) return e;
-  if (int e = check_rowmap(a->b_map, "mvlt_gemm_tn b_map")) return e;
-  MVLT_REQUIRE(a->a_map.mode == 0, "mvlt_gemm_tn: A cannot be a patch gather");
-  MVLT_REQUIRE(!(a->colsum_a && a->colsum_b), "mvlt_gemm_tn: at most one of colsum_a / colsum_b");
-  MVLT_REQUIRE(a->b_map.mode == 0 || a->N2 == a->b_map.r * a->b_map.r * a->b_map.c_seg, "mvlt_gemm_tn: gather N2 != r*r*c_seg");
-  MVLT_REQUIRE(a->c_taps <= 1 || (a->trans_c == 0 && a->c_seg > 0 && a->N2 == a->c_taps * a->c_seg), "mvlt_gemm_tn: c_taps needs trans_c == 0 and N2 == c_taps*c_seg");
-  MVLT_REQUIRE(!a->dgrad_out || (a->dtype == 0 && a->M < (1 << 24) && a->b_map.mode == 0 && a->a_map.mode == 0),
-               "mvlt_gemm_tn: dgrad_out rides on the bf16 LDS-DMA kernel only (bf16 operands, M < 2^24, plain row maps): every other path would leave it unwritten");
-  if (a->M == 0) return MVLT_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int mtiles = (a->M + TBK - 1) / TBK;
-  // a split of the LDS-DMA kernel must bring at least 8 k-tiles of work to its N1*N2 atomics: the kv / text-row weight gradients (32768 or 16384
-  // rows, 256 x 128 outputs) ran 256 splits of 1-2 k-tiles, 49 us where 32-64 splits take 20-26 us
-  constexpr int TN_MIN_TILES = 8;
-  // conv3x3 weight gradient with an LDS-resident halo (conv3_wgrad_kernel): 3x3 gather on B over a W x H grid with W in {8, 16, 32, 64},
-  // whole 64-pixel k-tiles inside one image, 64-multiples of channels, plain [out][tap*cin + c] output
-  if (a->dtype == 0 && a->b_map.mode == 2 && a->a_map.mode == 0 && a->a_map.rows_per_batch == 0 && !a->trans_c && a->c_taps <= 1 &&
-      !a->colsum_a && !a->colsum_b && a->N1 % 64 == 0 && a->b_map.c_seg % 64 == 0 && a->N2 == 9 * a->b_map.c_seg && a->M % 64 == 0 &&
-      (a->b_map.w_in == 8 || a->b_map.w_in == 16 || a->b_map.w_in == 32 || a->b_map.w_in == 64) && (a->b_map.h_in * a->b_map.w_in) % 64 == 0 &&
-      a->M % (a->b_map.h_in * a->b_map.w_in) == 0 && a->ldb >= a->b_map.c_seg) {
-    hipStream_t s2 = (hipStream_t)stream;
-    if (a->b_map.w_in == 64) return launch_conv3_wgrad<64>(*a, s2);
-    if (a->b_map.w_in == 32) return launch_conv3_wgrad<32>(*a, s2);
-    if (a->b_map.w_in == 16) return launch_conv3_wgrad<16>(*a, s2);
-    return launch_conv3_wgrad<8>(*a, s2);
-  }
-  // (Round 4 built this kernel's 8-wave / 8-phase sibling -- 256 x 256 and 128 x 320 output tiles, one workgroup per CU, commit 6d0e8d3 -- and
-  //  removed it again: its main loop ran at 1.1-1.16 PFLOP/s, but one workgroup per CU means 16 m-splits of the 2048 x 512 outputs, and the fp32
-  //  atomics that combine the splits complete at ~0.3 floats per ns chip-wide whatever their scope or coalescing: 55 us of tail per launch,
-  //  147 us against the 122 us of the 128 x 128 tiles below with their 8 splits and a second workgroup per CU to hide the tail.  DESIGN.md 6.)
-  // whole 256 x 256 output tiles, 16 .. 64 of them (= 16 .. 4 m-splits for one workgroup per CU), and a scratch buffer from the caller: the 8-wave / 8-phase TN loop with
-  // bf16 partial tiles + an ordered fold instead of fp32 atomics (gemm_tn_p8_kernel).  Fewer tiles mean more splits than the fold is
-  // worth (8 tiles: 75 us either way), more do not occur in this model.
-  if (a->partials && a->dtype == 0 && a->a_map.mode == 0 && a->b_map.mode == 0 && a->a_map.rows_per_batch == 0 && a->b_map.rows_per_batch == 0 && a->c_taps <= 1 &&
-      !a->trans_c && !a->dgrad_out && a->M % 64 == 0 && a->N1 % 256 == 0 && a->N2 % 256 == 0 && a->ldc % 4 == 0 && ((uintptr_t)a->C & 15) == 0 && ((uintptr_t)a->partials & 15) == 0) {
-    const int tiles = (a->N1 / 256) * (a->N2 / 256), nkt = a->M / 64;
-    if (tiles >= 16 && tiles <= 64 && nkt / (256 / tiles) >= 16 && a->partials_bytes >= (long)(256 / tiles) * a->N1 * a->N2 * 2)
-      return launch_tn_p8_partial<4, 2, 2>(*a, s);
-  }
-  // round 6: one side a multiple of 320, the other >= 1024 (the fc weight gradients of stage 3: 1280 x 320 and 320 x 1280): 192 x 320 tiles of the 8-phase TN loop, 6-16 of
-  // them, the last row tile ragged when it is >= 85 % full overall; bf16 partial tiles + the ordered fold (round 5 ran them on the 128-wide kernel)
-  if (a->partials && a->dtype == 0 && a->a_map.mode == 0 && a->b_map.mode == 0 && a->a_map.rows_per_batch == 0 && a->b_map.rows_per_batch == 0 && a->c_taps <= 1 &&
-      !a->trans_c && !a->dgrad_out && a->M % 64 == 0 && a->N1 % 8 == 0 && a->N2 % 8 == 0 && a->ldc % 4 == 0 && ((uintptr_t)a->C & 15) == 0 && ((uintptr_t)a->partials & 15) == 0 &&
-      a->lda % 8 == 0 && a->ldb % 8 == 0 && (((uintptr_t)a->A | (uintptr_t)a->B) & 15) == 0) {
-    const bool direct = a->N2 % 320 == 0 && a->N1 >= 1024, swapped = !direct && a->N1 % 320 == 0 && a->N2 >= 1024;
-    if (direct || swapped) {
-      const int rows = direct ? a->N1 : a->N2, cols = direct ? a->N2 : a->N1;
-      const int tiles = ((rows + 191) / 192) * (cols / 320), nkt = a->M / 64;
-      if (tiles >= 6 && tiles <= 16 && nkt / (256 / tiles) >= 16 && (double)rows >= 0.85 * 192.0 * ((rows + 191) / 192)) {
-        const int rc = direct ? launch_tn_p8_320<false>(*a, s) : launch_tn_p8_320<true>(*a, s);
-        if (rc <= 0) return rc;
-      }
-    }
-  }
-  if (a->dtype == 0 && a->M < (1 << 24)) {
-    // LDS-DMA kernel: A tile 128 or 64 wide, B tile 128 or 64 wide; ~1024 workgroups, splits a multiple of the 8 XCDs
-    // outputs of at most 128 x 128 take 64 x 64 tiles: every output cache line receives one atomic request per m-split, those
-    // serialise at the memory side (~100 ns each), and four small tiles need a quarter of the splits of one big tile for the same
-    // number of workgroups (294912 x 128 x 128: 61 -> 35 us)
-    if (a->dgrad_out) {
-      // weight gradient + input gradient of a C x C Linear from one pass over dY (gemm_tn_dma_kernel<.., DG>): one output tile, plain rows
-      MVLT_REQUIRE(a->dgrad_wt && a->N1 == a->N2 && (a->N1 == 64 || a->N1 == 128) && a->a_map.rows_per_batch == 0 && a->b_map.mode == 0 &&
-                   a->b_map.rows_per_batch == 0 && !a->trans_c && a->c_taps <= 1 && !a->colsum_b && a->dgrad_ld % 8 == 0 &&
-                   (((uintptr_t)a->dgrad_out | (uintptr_t)a->dgrad_wt) & 15) == 0,
-                   "mvlt_gemm_tn: dgrad_out needs bf16 operands, plain rows, N1 == N2 == 64 or 128, no transposed / tap output, 16-byte aligned buffers");
-      int splits = a->splits > 0 ? a->splits : (a->N1 == 64 ? 256 : 384);       // 1081344 x 64: 128 / 192 / 256 / 384 / 512 splits 136 / 90 / 83 / 91 / 85 us; 294912 x 128: 75 / 63 / 60 / 59 / 68
-      if (splits > mtiles / TN_MIN_TILES) splits = mtiles / TN_MIN_TILES;
-      if (splits >= 8) splits = (splits + 4) / 8 * 8;
-      if (splits > mtiles) splits = mtiles;
-      if (splits < 1) splits = 1;
-      const int m_per_split = ((mtiles + splits - 1) / splits) * TBK;
-      splits = (a->M + m_per_split - 1) / m_per_split;
-      dim3 grid((unsigned)(splits >= 8 ? 8 * ((splits + 7) / 8) : splits)), block(NTHREADS);
-      if (a->N1 == 64) {
-        const size_t lds = (size_t)4 * TBK * 128 * 2 + 64 * 64 * 2;
-        mvlt_max_lds<(gemm_tn_dma_kernel<64, 64, 3, 4, true>)>();
-        MVLT_LAUNCH((gemm_tn_dma_kernel<64, 64, 3, 4, true>), grid, block, lds, s, *a, m_per_split, 1, 1, splits, (bf16*)nullptr);
-      } else {
-        const size_t lds = (size_t)2 * TBK * 256 * 2 + 64 * 128 * 2;
-        mvlt_max_lds<(gemm_tn_dma_kernel<128, 128, 3, 2, true>)>();
-        MVLT_LAUNCH((gemm_tn_dma_kernel<128, 128, 3, 2, true>), grid, block, lds, s, *a, m_per_split, 1, 1, splits, (bf16*)nullptr);
-      }
-      return mvlt_check_launch("mvlt_gemm_tn");
-    }
-    MVLT_REQUIRE(!a->c_overwrite || (!a->trans_c && a->c_taps <= 1 && a->N2 % 4 == 0 && a->ldc % 4 == 0 && ((uintptr_t)a->C & 15) == 0),
-                 "mvlt_gemm_tn: c_overwrite needs the plain output layout, N2 % 4 == 0, ldc % 4 == 0 and a 16-byte aligned C");
-    const bool small_out = a->N1 <= 128 && a->N2 <= 128;
-    const int bmt = (a->N1 <= 64 || small_out) ? 64 : 128, bn = (a->N2 <= 64 || small_out) ? 64 : 128;
-    const int t1 = (a->N1 + bmt - 1) / bmt, t2 = (a->N2 + bn - 1) / bn;
-    int splits = a->c_overwrite ? 1 : a->splits;
-    if (splits <= 0) {
-      // 2 workgroups per CU in one round: every extra split is another N1*N2 fp32 atomics through the fabric
-      splits = ((t1 * t2 == 1 ? 384 : 512) + t1 * t2 - 1) / (t1 * t2);     // a single output tile: 384 (1081344 x 64 x 64: 54.7 -> 48.9 us)
-      if (splits >= 8) splits = (splits + 4) / 8 * 8;
-      if (splits > 4096) splits = 4096;
-      if (splits > mtiles / TN_MIN_TILES) splits = mtiles / TN_MIN_TILES;
-    }
-    if (splits > mtiles) splits = mtiles;
-    if (splits < 1) splits = 1;
-    int m_per_split = ((mtiles + splits - 1) / splits) * TBK;
-    splits = (a->M + m_per_split - 1) / m_per_split;
-    const int ns = (bmt + bn == 256) ? 2 : (bmt + bn == 192) ? 3 : 4;      // 64 / 72 / 64 KB of LDS: 2 workgroups per CU
-    const size_t lds = (size_t)ns * TBK * (bmt + bn) * 2;
-    dim3 grid((unsigned)((splits >= 8 ? 8 * ((splits + 7) / 8) : splits) * t1 * t2)), block(NTHREADS);
-    // several splits meeting on an output of >= 65536 elements (>= 8: the C x C and the fc weight gradients of stages 3-4; 24 while every fold was a launch of its own -- with the
-    // batched folds 16 / 8 / 4 / 2 all measure 12.98-13.00 k pairs/s against 12.90 at 24): bf16 partial tiles into the caller's scratch
-    // + an ordered fold instead of the atomics (14-21 us of a 53-56 us launch, profiles/r05_tn_small_atomics_ablation.txt).  Fewer splits: the atomics are cheaper than a fold launch.
-    constexpr int part_min = 8;
-    // ... and from 16384 output elements on (65536 through round 5): the SMALL outputs are where many splits hurt most -- text_embed1's 64 x 768 weight gradient over 32768 rows:
-    // 64 splits x 49152 atomics on the same 1536 cache lines = 56 us where its operands are 9 us of HBM time (tools/ubench_tn_smallk.py)
-    constexpr long part_min_out = 16384;
-    bf16* const part = (a->partials && !a->c_overwrite && splits >= part_min && !a->trans_c && a->c_taps <= 1 && a->N2 % 8 == 0 && a->ldc % 4 == 0 && ((uintptr_t)a->C & 15) == 0 &&
-                        (long)a->N1 * a->N2 >= part_min_out)
-                           ? fold_acquire(*a, (long)splits * a->N1 * a->N2 * 2, s) : nullptr;
-#define MVLT_TN_LAUNCH(BMT_, BN_, NS_)                                                                                          \
-  do {                                                                                                                         \
-    if (a->b_map.mode == 0 && a->b_map.rows_per_batch == 0 && a->a_map.rows_per_batch == 0)                                                        \
-      MVLT_LAUNCH((gemm_tn_dma_kernel<BMT_, BN_, 3, NS_>), grid, block, lds, s, *a, m_per_split, t1, t2, splits, part);                     \
-    else if (a->b_map.mode == 0) MVLT_LAUNCH((gemm_tn_dma_kernel<BMT_, BN_, 0, NS_>), grid, block, lds, s, *a, m_per_split, t1, t2, splits, part); \
-    else if (a->b_map.mode == 1) MVLT_LAUNCH((gemm_tn_dma_kernel<BMT_, BN_, 1, NS_>), grid, block, lds, s, *a, m_per_split, t1, t2, splits, part); \
-    else MVLT_LAUNCH((gemm_tn_dma_kernel<BMT_, BN_, 2, NS_>), grid, block, lds, s, *a, m_per_split, t1, t2, splits, part);                   \
-  } while (0)
-    if (bmt == 128 && bn == 128) MVLT_TN_LAUNCH(128, 128, 2);
-    else if (bmt == 128) MVLT_TN_LAUNCH(128, 64, 3);
-    else if (bn == 128) MVLT_TN_LAUNCH(64, 128, 3);
-    else MVLT_TN_LAUNCH(64, 64, 4);
-#undef MVLT_TN_LAUNCH
-    if (part) fold_launch(*a, part, splits, s);
-    return mvlt_check_launch("mvlt_gemm_tn");
-  }
-  const bool narrow = a->N2 <= 64;
-  const int bn = narrow ? 64 : 128;
-  const int t1 = (a->N1 + BM - 1) / BM, t2 = (a->N2 + bn - 1) / bn;
-  int splits = a->splits;
-  if (splits <= 0) {
-    splits = (1024 + t1 * t2 - 1) / (t1 * t2);       // ~4 workgroups per CU in total
-    if (splits > mtiles) splits = mtiles;
-    if (splits > 4096) splits = 4096;
-    if (splits < 1) splits = 1;
-  }
-  int m_per_split = ((mtiles + splits - 1) / splits) * TBK;
-  splits = (a->M + m_per_split - 1) / m_per_split;
-  const int rowb = a->dtype == 0 ? TElem<bf16>::ROWB : TElem<float>::ROWB;
-  const size_t lds = (size_t)(BM + bn) * rowb + BM * sizeof(float);
-  dim3 grid((unsigned)t1, (unsigned)t2, (unsigned)splits), block(NTHREADS);
-  if (a->dtype == 0) {
-    if (narrow) MVLT_LAUNCH((gemm_tn_kernel<bf16, 64>), grid, block, lds, s, *a, m_per_split);
-    else MVLT_LAUNCH((gemm_tn_kernel<bf16, 128>), grid, block, lds, s, *a, m_per_split);
-  } else {
-    if (narrow) MVLT_LAUNCH((gemm_tn_kernel<float, 64>), grid, block, lds, s, *a, m_per_split);
-    else MVLT_LAUNCH((gemm_tn_kernel<float, 128>), grid, block, lds, s, *a, m_per_split);
-  }
-  return mvlt_check_launch("mvlt_gemm_tn");
-}

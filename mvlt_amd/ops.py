@@ -1,4 +1,4 @@
-"""Thin Python calls over the C ABI (include/mvlt_hip.h).  Every function launches HIP kernels asynchronously on
+"""Thin Python calls over the C ABI (include/mvlt_hip.h and the additions beside it).  Every function launches HIP kernels asynchronously on
 torch's current stream; tensors are only used as device buffers.  No fallbacks: a missing library or a CPU tensor
 raises (mvlt_amd/_lib.py)."""
 import ctypes as C
@@ -11,10 +11,9 @@ from ._lib import DT, check, patchmap, ptr, rowmap, stream_ptr
 _ID = rowmap()
 
 
-def gemm_nt(A, B, C_out, M, N, K, lda, ldb, ldc, *, a_map=None, c_map=None, bias=None, act=0, H=None,
-            row_scale=None, rows_per_scale=0, R=None, col_sum=None, col_sumsq=None, col_copies=0, split_k=0, post_ln=None):
-    """C[M,N] = epi(A[M,K] @ B[N,K]^T); see mvlt_gemm_nt in include/mvlt_hip.h.  post_ln = (gamma, beta, eps, y, mean, rstd): LayerNorm of the
-    finished output rows rides on the epilogue (N == 64 / 128, bf16 operands, R given)."""
+def _gemm_nt_args(A, B, C_out, M, N, K, lda, ldb, ldc, *, a_map=None, c_map=None, bias=None, act=0, H=None,
+                  row_scale=None, rows_per_scale=0, R=None, col_sum=None, col_sumsq=None, col_copies=0, split_k=0, post_ln=None):
+    """the mvlt_gemm_nt_args of a gemm_nt / gemm_nt_plan call"""
     assert A.dtype == B.dtype and A.dtype in DT and (C_out.dtype in DT or (C_out.dtype == torch.float16 and col_sum is not None))
     if bias is not None:
         assert bias.dtype == torch.float32
@@ -36,8 +35,39 @@ def gemm_nt(A, B, C_out, M, N, K, lda, ldb, ldc, *, a_map=None, c_map=None, bias
         g, b, eps, y, mean, rstd = post_ln
         assert g.dtype == b.dtype == mean.dtype == rstd.dtype == torch.float32 and y.dtype == torch.bfloat16 and y.is_contiguous()
         a.post_y, a.post_ld, a.post_gamma, a.post_beta, a.post_eps, a.post_mean, a.post_rstd = ptr(y), y.shape[-1], ptr(g), ptr(b), eps, ptr(mean), ptr(rstd)
-    check(L.lib.mvlt_gemm_nt(C.byref(a), stream_ptr()), "mvlt_gemm_nt")
+    return a
+
+
+def gemm_nt(A, B, C_out, *dims, **kw):
+    """gemm_nt(A, B, C_out, M, N, K, lda, ldb, ldc, *, a_map, c_map, bias, act, H, row_scale, rows_per_scale, R, col_sum, col_sumsq, col_copies, split_k, post_ln):
+    C[M,N] = epi(A[M,K] @ B[N,K]^T); see mvlt_gemm_nt in include/mvlt_hip.h.  post_ln = (gamma, beta, eps, y, mean, rstd): LayerNorm of the
+    finished output rows rides on the epilogue (N == 64 / 128, bf16 operands, R given)."""
+    check(L.lib.mvlt_gemm_nt(C.byref(_gemm_nt_args(A, B, C_out, *dims, **kw)), stream_ptr()), "mvlt_gemm_nt")
     return C_out
+
+
+class Plan:
+    """what a GEMM call would launch (mvlt_gemm_plan of include/mvlt_hip_plan.h): .name is the kernel as _lib.last_kernel() prints it, .p the struct"""
+
+    def __init__(self, plan_fn, args):
+        p, buf = L.GemmPlan(), C.create_string_buffer(256)
+        check(plan_fn(C.byref(args), C.byref(p)), "mvlt_gemm_plan")
+        check(min(L.lib.mvlt_gemm_plan_name(C.byref(p), buf, len(buf)), 0), "mvlt_gemm_plan_name")
+        self.p, self.name = p, buf.value.decode()
+
+    def __getattr__(self, field):
+        v = getattr(self.p, field)
+        return v if isinstance(v, int) else list(v)
+
+
+def gemm_nt_plan(*args, **kw):
+    """same arguments as gemm_nt; nothing is launched and no device is touched"""
+    return Plan(L.lib.mvlt_gemm_nt_plan, _gemm_nt_args(*args, **kw))
+
+
+def gemm_tn_plan(*args, **kw):
+    """same arguments as gemm_tn; nothing is launched and no device is touched"""
+    return Plan(L.lib.mvlt_gemm_tn_plan, _gemm_tn_args(*args, **kw))
 
 
 def tn_fold_flush(partials=None):
@@ -57,12 +87,19 @@ def weight_prep(desc_dev, blk_dev, ndesc, total_blocks, dtype, blk_desc=None):
     check(L.lib.mvlt_weight_prep(ptr(desc_dev), ptr(blk_dev), ndesc, total_blocks, ptr(blk_desc), DT[dtype], stream_ptr()), "mvlt_weight_prep")
 
 
-def gemm_tn(A, B, C_out, M, N1, N2, lda, ldb, ldc, *, a_map=None, b_map=None, colsum=None, splits=0, taps=0, seg=0, dgrad=None, partials=None, defer_fold=False, overwrite=False):
-    """C[N1,N2] += A[M,N1]^T @ B[M,N2] (fp32 atomics); colsum[N1] += A.sum(0).  taps > 1: logical column tap*seg + c is
+def gemm_tn(A, B, C_out, *dims, **kw):
+    """gemm_tn(A, B, C_out, M, N1, N2, lda, ldb, ldc, *, a_map, b_map, colsum, splits, taps, seg, dgrad, partials, defer_fold, overwrite):
+    C[N1,N2] += A[M,N1]^T @ B[M,N2] (fp32 atomics); colsum[N1] += A.sum(0).  taps > 1: logical column tap*seg + c is
     accumulated at column c*taps + tap (conv weight gradients straight into the [out][cin][kh][kw] layout).
     dgrad = (W^T [N2][N1] bf16, out [M, N2] bf16): the Linear's input gradient out = A @ W from the same pass over A (N1 == N2 in {64, 128}).
     partials = a scratch tensor (the largest single launch of the model needs 37 MiB; deferring launches share it region by region: FlatStore holds 256 MiB): split reductions leave as bf16 partial tiles + an ordered fold instead of fp32 atomics where the
     library has that mode (mvlt_gemm_tn_args.partials in include/mvlt_hip.h: whole 256 x 256 tiles, >= 8 m-splits on the 128-wide kernel, conv3x3 weight gradients); deterministic."""
+    check(L.lib.mvlt_gemm_tn(C.byref(_gemm_tn_args(A, B, C_out, *dims, **kw)), stream_ptr()), "mvlt_gemm_tn")
+    return C_out
+
+
+def _gemm_tn_args(A, B, C_out, M, N1, N2, lda, ldb, ldc, *, a_map=None, b_map=None, colsum=None, splits=0, taps=0, seg=0, dgrad=None, partials=None, defer_fold=False, overwrite=False):
+    """the mvlt_gemm_tn_args of a gemm_tn / gemm_tn_plan call"""
     assert A.dtype == B.dtype and A.dtype in DT and C_out.dtype == torch.float32
     if colsum is not None:
         assert colsum.dtype == torch.float32
@@ -93,8 +130,7 @@ def gemm_tn(A, B, C_out, M, N1, N2, lda, ldb, ldc, *, a_map=None, b_map=None, co
     if overwrite and dgrad is None:
         assert not a.trans_c and taps <= 1 and N2 % 4 == 0 and ldc % 4 == 0 and A.dtype == torch.bfloat16, "gemm_tn(overwrite=True): bf16, plain output layout, N2 and ldc multiples of 4"
         a.c_overwrite = 1                               # C_out holds zeros (the caller's word): one m-split, plain stores instead of atomics
-    check(L.lib.mvlt_gemm_tn(C.byref(a), stream_ptr()), "mvlt_gemm_tn")
-    return C_out
+    return a
 
 
 LN_CHAIN_WIDTHS = (64, 128, 320, 512, 768)     # widths with a fixed-geometry forward kernel: these can chain a second LayerNorm

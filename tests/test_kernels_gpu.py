@@ -90,6 +90,83 @@ def test_gemm_nt_epilogues(ops, dtype, N):
         assert torch.equal(o16, o32.to(dtype))
 
 
+def _conv3_gather(x, Bsz, Hh, Ww):
+    """[pixels][9 C] rows of the 3x3 / pad 1 neighbourhood gather (tap-major) of a pixel-major [B Hh Ww][C] map"""
+    xp = F.pad(x.float().view(Bsz, Hh, Ww, -1), (0, 0, 1, 1, 1, 1))
+    return torch.cat([xp[:, dy:dy + Hh, dx:dx + Ww] for dy in range(3) for dx in range(3)], dim=-1).reshape(Bsz * Hh * Ww, -1)
+
+
+# one shape per launch family of mvlt_gemm_nt / mvlt_gemm_tn (whole / ragged and direct / swapped variants of the 8-phase tiles): the smallest whose plan is that
+# family (tests/test_gemm_plan_cpu.py pins the plans on the CPU); (family the shape is meant for, op, sizes, what else)
+PLAN_CASES = [
+    ("gemm_nt_kernel<float", "nt", (256, 128, 64), dict(dtype=torch.float32)),
+    ("gemm_nt_dma_kernel<128", "nt", (300, 128, 128), {}),
+    ("gemm_nt_p8_kernel<1, 4, 2, 2, false>", "nt", (16384, 768, 128), {}),
+    ("gemm_nt_p8_kernel<1, 3, 2, 2, false>", "nt", (12288, 1024, 128), {}),
+    ("gemm_nt_p8_kernel<1, 3, 3, 2, false>", "nt", (36864, 320, 128), {}),
+    ("gemm_nt_p8_kernel<1, 4, 2, 2, true>", "nt", (13928, 2048, 128), {}),
+    ("gemm_nt_p8_kernel<1, 3, 3, 2, true>", "nt", (41784, 320, 128), {}),
+    ("conv3_nt_kernel<16, 64, 1>", "nt", (256, 64, 576), dict(conv=(1, 16, 16, 64))),
+    ("gemm_tn_kernel<float", "tn", (256, 128, 128), dict(dtype=torch.float32)),
+    ("gemm_tn_dma_kernel<64, 64, 3, 4, false>", "tn", (4096, 128, 128), {}),
+    ("gemm_tn_dma_kernel<64, 64, 3, 4, false>", "tn", (4096, 128, 128), dict(partials=1 << 20)),
+    ("gemm_tn_dma_kernel<64, 64, 3, 4, true>", "tn", (4096, 64, 64), dict(dgrad=True)),
+    ("gemm_tn_p8_kernel<4, 2, 2, true, false, false>", "tn", (16384, 1024, 1024), dict(partials=32 << 20)),
+    ("gemm_tn_p8_kernel<3, 3, 2, true, true, false>", "tn", (36864, 1280, 320), dict(partials=32 << 20)),
+    ("gemm_tn_p8_kernel<3, 3, 2, true, false, false>", "tn", (43008, 1152, 320), dict(partials=32 << 20)),
+    ("gemm_tn_p8_kernel<3, 3, 2, false, true, true>", "tn", (36864, 320, 1280), dict(partials=32 << 20)),
+    ("gemm_tn_p8_kernel<3, 3, 2, false, false, true>", "tn", (43008, 320, 1152), dict(partials=32 << 20)),
+    ("conv3_wgrad_kernel<16>", "tn", (1024, 64, 576), dict(conv=(4, 16, 16, 64))),
+]
+
+
+@pytest.mark.parametrize("family, op, sizes, extra", PLAN_CASES, ids=[f"{c[1]}-{'x'.join(map(str, c[2]))}-{'-'.join(c[3]) or 'plain'}" for c in PLAN_CASES])
+def test_gemm_runs_what_its_plan_names(ops, family, op, sizes, extra):
+    """ops.gemm_*_plan(...) names the kernel the same call then launches, and the result is the fp32 product within the file's tolerance.  A launch that leaves
+    partial tiles runs with defer_fold: its fold is then an entry of the pending table, not a launch, so the GEMM is still the kernel launched last; the flush folds"""
+    from mvlt_amd._lib import conv3map, last_kernel
+    dt = extra.get("dtype", torch.bfloat16)
+    g = torch.Generator(device=dev()).manual_seed(sum(sizes))
+    rand = lambda *shape: torch.randn(*shape, device=dev(), generator=g).to(dt)
+    conv = extra.get("conv")
+    kw = {}
+    if op == "nt":
+        M, N, K = sizes
+        A, W = rand(M, conv[3] if conv else K), rand(N, K) * 0.2
+        out = torch.empty(M, N, device=dev(), dtype=dt)
+        if conv:
+            kw["a_map"] = conv3map(conv[1], conv[2], conv[1] * conv[2], conv[3])
+        args = (A, W, out, M, N, K, A.shape[1], K, N)
+        ref = (_conv3_gather(A, *conv[:3]) if conv else A.float()) @ W.float().t()
+        plan, run = ops.gemm_nt_plan, ops.gemm_nt
+    else:
+        M, N1, N2 = sizes
+        A, B = rand(M, N1), rand(M, conv[3] if conv else N2)
+        out = torch.zeros(N1, N2, device=dev())
+        if conv:
+            kw["b_map"] = conv3map(conv[1], conv[2], conv[1] * conv[2], conv[3])
+        if "partials" in extra:
+            kw.update(partials=torch.empty(extra["partials"], device=dev(), dtype=torch.uint8), defer_fold=True)
+        if extra.get("dgrad"):
+            Wt = rand(N2, N1) * 0.2
+            kw["dgrad"] = (Wt, torch.empty(M, N2, device=dev(), dtype=dt))
+        args = (A, B, out, M, N1, N2, N1, B.shape[1], N2)
+        ref = A.float().t() @ (_conv3_gather(B, *conv[:3]) if conv else B.float())
+        plan, run = ops.gemm_tn_plan, ops.gemm_tn
+    planned = plan(*args, **kw)
+    name = planned.name
+    assert name.startswith(family), (name, family)
+    run(*args, **kw)
+    assert name in last_kernel(), (name, last_kernel())
+    assert planned.fold == ("partials" in kw)
+    if planned.fold:
+        ops.tn_fold_flush(kw["partials"])
+        assert "tn_fold_multi_kernel" in last_kernel()
+    assert maxrel(out.float(), ref) < TOL[dt], (name, maxrel(out.float(), ref))
+    if extra.get("dgrad"):
+        assert maxrel(kw["dgrad"][1].float(), A.float() @ Wt.float().t()) < TOL[dt]
+
+
 @pytest.mark.parametrize("M,N,K,ldc", [(1490, 30522, 768, 30528), (257, 98309, 128, 98312), (1024, 24580, 192, 24584), (1490, 3002, 768, 3008)])
 @pytest.mark.parametrize("odt", [torch.float32, torch.bfloat16])
 def test_gemm_nt_ragged_rows_and_columns(ops, M, N, K, ldc, odt):
