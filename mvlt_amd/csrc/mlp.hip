@@ -827,9 +827,17 @@ __global__ __launch_bounds__(NT, C == 64 ? 2 : 1) void mlp_wgrad_kernel(mvlt_mlp
     const char* tX = sT + slot * STAGE;
     const char* tY = tX + TILE;
 
-    // per-sample DropPath factor of this lane's 16 token rows (16 mt + 4 fg + r): a tile spans at most two samples
+    // per-sample DropPath factor of this lane's 16 token rows (16 mt + 4 fg + r).  From 63 rows per sample on a 64-row tile spans at most two samples:
+    // two scalar loads and a compare per row.  Shorter samples (stage 2 of a 64 x 32 px input with T = 20 has 52 rows per sample: a tile can hold the tail of
+    // one, all of the next and the head of a third) look the factor up per row; the index is clamped to the last sample for the rows past M, which hold zeros.
     float sc[4][4];
-    if (scaled) {
+    if (scaled && p.rows_per_scale < 63) {
+      const int last = (p.M - 1) / p.rows_per_scale;
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sc[mt][r] = p.row_scale[min((mt0 + mt * 16 + 4 * fg + r) / p.rows_per_scale, last)];
+    } else if (scaled) {
       const int b0 = __builtin_amdgcn_readfirstlane(mt0 / p.rows_per_scale);
       const int bound = (b0 + 1) * p.rows_per_scale;
       const int b1i = __builtin_amdgcn_readfirstlane(min(b0 + 1, (p.M - 1) / p.rows_per_scale));

@@ -4,7 +4,8 @@ With operands of magnitude <= 3 every product and every partial sum is an intege
 split-K, m-splits and ordered folds must reproduce the float64 reference bit for bit, a bf16 / fp16 output is the exact result rounded once to
 nearest-even, and one dropped, doubled or misaddressed element is a hard mismatch with a row and a column to print.  Every GEMM case asserts the kernel
 family it meant to reach through mvlt_amd._lib.last_kernel(): a case that silently falls to another kernel fails instead of testing nothing.
-(The GELU epilogues, act 1 / 2, are not exact and stay with the tolerance tests of test_kernels_gpu.py.)"""
+(The GELU epilogues, act 1 / 2, are not exact on N(0,1) data and stay with the tolerance tests of test_kernels_gpu.py; on saturated data they and the fused MLP
+are: test_mlp_exact_gpu.py.)"""
 import ctypes as C_
 
 import pytest

@@ -1097,7 +1097,9 @@ def test_transpose_cast(ops, dtype):
 @pytest.mark.parametrize("Cdim,hid,M,Bsz", [(64, 512, 3 * 400, 3), (128, 1024, 2 * 333, 2), (64, 512, 130, 1),
                                             # samples of whole 64-token tiles (what the model's stages give: 4224 / 1152 rows per sample): the
                                             # round-3 weight-gradient kernel (tile-uniform DropPath factor, dropped samples skipped); the last
-                                            # case has two DIFFERENT non-zero factors (the accumulator-rescale branch)
+                                            # case has two DIFFERENT non-zero factors, but every workgroup of these shapes owns ONE 64-token tile,
+                                            # so the accumulator-rescale branch (two factors inside one split) is not reached here: the
+                                            # multi-tile cases of test_mlp_exact_gpu.py reach it
                                             (64, 512, 3 * 448, 3), (128, 1024, 3 * 320, 3), (64, 512, 4 * 192, 4)])
 def test_fused_mlp(ops, Cdim, hid, M, Bsz):
     bf = torch.bfloat16
