@@ -19,7 +19,7 @@ extern "C" {
 #define MVLT_PLAN_VERSION 1
 int mvlt_plan_version(void);
 
-/* kernel families of mvlt_amd/csrc/gemm.hip; tp[] holds the template arguments of the instantiation in the order the kernel declares them
+/* kernel families of the GEMMs (mvlt_amd/csrc/gemm_<family>.hip, dispatched by gemm.hip); tp[] holds the template arguments of the instantiation in the order the kernel declares them
  * (bool as 0 / 1, an element type as its dtype code) */
 #define MVLT_GEMM_NONE 0        /* M == 0: nothing to launch */
 #define MVLT_GEMM_NT_F32 1      /* gemm_nt_kernel<float, BN>                           tp = {BN} */

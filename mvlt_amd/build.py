@@ -59,7 +59,7 @@ def _compile(src, force, verbose):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     srcs = _sources()
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(6, len(srcs))) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
         objs = list(ex.map(lambda s: _compile(s, force, verbose), srcs))
     if force or not os.path.exists(LIB) or any(os.path.getmtime(o) > os.path.getmtime(LIB) for o in objs):
         cmd = ["hipcc", "--offload-arch=" + ARCH, "-shared", "-fPIC", *objs, "-o", LIB]

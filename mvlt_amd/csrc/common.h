@@ -85,7 +85,7 @@ template <auto K> inline void mvlt_max_lds() {
   done.fetch_or(bit, std::memory_order_relaxed);
 }
 
-// partial-tile reductions of the weight-gradient kernels (gemm.hip): the scratch region for `need` bytes of bf16 partial tiles of the output a.C [a.N1][a.N2] (nullptr: they do
+// partial-tile reductions of the weight-gradient kernels (gemm.hip; the kernels themselves: gemm_tn_*.hip, gemm_conv3.hip): the scratch region for `need` bytes of bf16 partial tiles of the output a.C [a.N1][a.N2] (nullptr: they do
 // not fit / no scratch), and the fold of `splits` tiles [splits][N1][N2] into it (at once, or appended to the scratch's pending table: a.defer_fold).  Also used by mlp.hip.
 struct mvlt_gemm_tn_args;
 bf16* mvlt_fold_acquire_ext(const mvlt_gemm_tn_args& a, long need, hipStream_t s, int descriptors);       // room for that many fold_launch calls behind it
@@ -162,6 +162,9 @@ __device__ __forceinline__ void gelu_erf_both2(f32x2 x, f32x2& g, f32x2& dg) {
 // GELU'(4) = 1 + 5.0e-4), near-minimax fits (the fitting recipe is in DESIGN 6.0).  v_exp_f32 / v_rcp_f32 cost 2.3 plain VALU
 // instructions each on gfx950 (profiles/r03_valu_rates.txt): GELU' is 10 plain instructions here against 15 + 2 transcendentals
 // (19.6 units) above.  |GELU' error| <= 2.8e-4 + the 5e-4 tail, |Phi error| <= 1.0e-4 absolute (fp32 Horner).
+// In the bf16 GEMM epilogues (EPI 3 / 4, gemm_common.h) round 3 measured no gain on the 128-wide kernels (four workgroups per CU hide the epilogue's VALU work); on the
+// 8-wave kernels (two waves per SIMD, VALU-bound epilogue) GELU' is 10 instructions instead of 19.6 issue units: stage-4 GELU' dgrad 179 -> 157 us, stage-3 204 -> 181 us
+// (same-box A/B, round 4).  One default for the GEMM and the fused-MLP kernels; tools/parity_orderings.sh builds the other arithmetic ordering with it.
 #ifndef MVLT_GELU_POLY
 #define MVLT_GELU_POLY 3
 #endif

@@ -1,6 +1,6 @@
 // Host side of mvlt_gemm_nt / mvlt_gemm_tn: argument checks, then the choice of kernel family, template arguments, launch geometry and trailing kernel
 // arguments -- a pure function of the argument struct (no HIP call, no global state, no launch; plain C++17, compiles with a host compiler alone).
-// gemm.hip launches what a plan says (one case list per entry point, no shape condition there); include/mvlt_hip_plan.h exports the plan, and
+// gemm.hip hands a plan to its family's file (gemm_<family>.hip: one case list per family and entry point, no shape condition there); include/mvlt_hip_plan.h exports the plan, and
 // tests/test_gemm_plan_cpu.py pins it against launches recorded on an MI355X.  The measured knowledge of the dispatch lives HERE; DESIGN.md ("GEMM dispatch: plan, then launch") has the table of families.
 #pragma once
 #include <stdint.h>
@@ -31,7 +31,7 @@ constexpr int ROW_BYTES = 128;        // one LDS row = 128 B of K
 constexpr int TBK = 64;               // reduction rows per LDS tile of the TN kernels (both dtypes)
 constexpr int TN_ROWB_BF16 = (TBK + 8) * 2, TN_ROWB_F32 = (TBK + 4) * 4;      // padded LDS rows of the register-staged TN kernel: 144 B / 272 B
 constexpr int TN_TILE64_BYTES = TBK * 64 * 2;                                 // a 64-column bf16 tile of the LDS-DMA TN kernels
-// (the kernels' own constants of these names and TElem<>::ROWB / DmaTile<64>::BYTES: gemm.hip static_asserts that they agree)
+// (the kernels' own constants of these names and TElem<>::ROWB / DmaTile<64>::BYTES: gemm_common.h static_asserts that they agree)
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -1,6 +1,6 @@
 """Test infrastructure: operands, float64 references and bounds of the exact fused-MLP tests (tests/test_mlp_exact_gpu.py; the premises are pinned on
 the CPU by tests/test_mlp_cases_cpu.py).  The kernels: csrc/mlp.hip (mlp_fused_kernel, mlp_pipe_kernel, mlp_wgrad_kernel, mlp_wgrad2_kernel), the GELU
-epilogues of csrc/gemm.hip and gelu_bwd.  Plain torch on the CPU, no GPU and no library.  The argument is written down in docs/mlp_exact.md.
+epilogues of the NT GEMMs (csrc/gemm_common.h: nt_epilogue_lean) and gelu_bwd.  Plain torch on the CPU, no GPU and no library.  The argument is written down in docs/mlp_exact.md.
 
 Every pre-activation is SATURATED: an integer h with |h| >= SAT.  For a unit that is on (h >= SAT) every GELU form of the tree gives Phi and GELU' within
 2^-9 of 1, so the bf16 tile the kernels keep holds h (forward) and dG (backward) exactly and the MLP is two integer GEMMs.  For a unit that is off

@@ -118,10 +118,18 @@ def test_every_recorded_launch_is_planned_exactly():
 
 # ---- every instantiation of the launch switches is pinned
 
+FAMILY_FILES = ("gemm_nt_dma.hip", "gemm_nt_p8.hip", "gemm_tn_dma.hip", "gemm_tn_p8.hip", "gemm_conv3.hip")
+
+
+def _launch_side(name):
+    """a GEMM translation unit from its "plan -> launch" heading to its end"""
+    src = open(os.path.join(ROOT, "mvlt_amd", "csrc", name)).read()
+    return src[src.index("plan -> launch"):]
+
+
 def _switch_instantiations():
-    """the kernel names behind the case lists of launch_nt / launch_tn in gemm.hip, as mvlt_gemm_plan_name prints them"""
-    src = open(os.path.join(ROOT, "mvlt_amd", "csrc", "gemm.hip")).read()
-    body = src[src.index("plan -> launch"):src.index('extern "C" int mvlt_gemm_nt(')]
+    """the kernel names behind the case lists of the family files' launch functions, as mvlt_gemm_plan_name prints them"""
+    body = "\n".join(_launch_side(f) for f in FAMILY_FILES)
     body = "\n".join(x for x in re.sub(r"\\\n", " ", body).split("\n") if not x.lstrip().startswith("#"))          # the case lists, without the macro definitions
     epis = lambda bn, am: [("NT_DMA", bn, am, e, "64") for e in "12345670"]
     conv = lambda w: [("NT_CONV3", w, bn, e) for bn, es in (("192", "15"), ("64", "125"), ("128", "125")) for e in es]
@@ -376,8 +384,7 @@ def test_plan_is_host_only_and_the_launch_side_chooses_nothing():
     assert cxx, "a host C++ compiler"
     r = subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-x", "c++", plan_h], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    src = open(os.path.join(ROOT, "mvlt_amd", "csrc", "gemm.hip")).read()
-    launch = re.sub(r"//[^\n]*", "", src[src.index("plan -> launch"):])
+    launch = re.sub(r"//[^\n]*", "", "\n".join(_launch_side(f) for f in ("gemm_common.h", "gemm.hip") + FAMILY_FILES))
     for word in ("a.M", "a.K", "a->", "0.85", "16384", "TN_MIN_TILES", "part_min", ">= 192", "% 320", "<= 512", ">= 640"):
         assert word not in launch, word
 

@@ -1,5 +1,5 @@
 """The q / proj / kv weight-gradient shapes of stages 3-4 (outputs of 320 x 320 .. 1024 x 512) alone: how much of the launch is the split reduction?
-A/B against an ablation build without the output atomics: MVLT_HIP_LIB=ab/libmvlt_tnnoat.so (tools/build_alt.sh tnnoat gemm.hip -DMVLT_TN_NOATOMIC=1)."""
+A/B against an ablation build without the output atomics: MVLT_HIP_LIB=ab/libmvlt_tnnoat.so (tools/build_alt.sh tnnoat gemm_tn_dma.hip,gemm_tn_p8.hip -DMVLT_TN_NOATOMIC=1)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mvlt_amd import ops
