@@ -344,7 +344,7 @@ class FlatStore:
                 ops.tn_fold_discard(self._tn_partials)         # THIS store's folds (the table is kept per scratch) a pass that raised left pending (nothing, normally): dropped, never run -- their gradients are void, their buffers may be gone
         live = [(n, q) for n, q in self.fn_params if q.requires_grad]
         alias = [q.grad is not None and q.grad.data_ptr() == self.grad(n).data_ptr() for n, q in live]
-        self.all_zeroed_this_pass = not any(alias)     # G is all zeros now: a pass's FIRST writer of a slice may store instead of add (schedule._mlm_decoder_bwd)
+        self.all_zeroed_this_pass = not any(alias)     # G is all zeros now: a pass's FIRST writer of a slice may store instead of add (heads._mlm_decoder_bwd)
         self.touched_this_pass = set()
         if not any(alias):
             self.G.zero_()

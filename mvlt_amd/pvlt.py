@@ -21,6 +21,7 @@ import torch.nn as nn
 from . import ops
 from ._lib import patchmap, rowmap
 from .params import FlatStore, Holder, affine, conv_default_init_, linear, trunc_normal_
+from .plan import stage_grids
 
 __all__ = ["pvlt_tiny", "pvlt_small", "pvlt_medium", "pvlt_large", "PyramidVisionLanguageTransformer"]
 
@@ -255,7 +256,7 @@ class PyramidVisionLanguageTransformer(nn.Module):
         if not input_images.is_cuda:
             raise RuntimeError("mvlt_amd PVLT runs on MI355X only (HIP kernels); there is no CPU path. "
                                "Use oracle/pvlt_oracle.py for CPU checks.")
-        from .schedule import run_forward
+        from .schedule import run_forward            # (lazy: schedule -> trunk / heads import this module's constants)
         return run_forward(self, input_images, input_ids, mlm_labels, mlm_positions, mlm_count, t2i_target)
 
 
@@ -266,7 +267,7 @@ class PyramidVisionLanguageTransformer(nn.Module):
         token buffers to the heads directly)."""
         if not x.is_cuda:
             raise RuntimeError("mvlt_amd PVLT runs on MI355X only (HIP kernels); there is no CPU path.")
-        from .schedule import run_trunk, stage_grids
+        from .schedule import run_trunk
         outs = run_trunk(self, x, y)
         B = x.shape[0]
         img_feats, text_feats = [], []

@@ -156,7 +156,7 @@ def test_late_maximum_in_the_last_key_block(ops, dtype, boost):
 
 
 def test_one_chunk_bf16_dkv_writes_every_element(ops):
-    """where mvlt_sr_attention_bwd_chunks says 1 the caller may hand a bf16 dKV (mvlt_amd/schedule.py does): every element stored once"""
+    """where mvlt_sr_attention_bwd_chunks says 1 the caller may hand a bf16 dKV (mvlt_amd/trunk.py does): every element stored once"""
     B, H, N, M = 4, 8, 128, 384
     assert ops.sr_attention_bwd_chunks(B, H, N, M, BF) == 1
     q, kv, do = data(B, H, N, M, BF)

@@ -1,7 +1,10 @@
-"""No GPU: frozen parameters (requires_grad=False) -- the pure-Python backward plan (mvlt_amd.schedule.backward_plan) for the settings a fine-tune run
+"""No GPU: frozen parameters (requires_grad=False) -- the pure-Python backward plan (mvlt_amd.plan.backward_plan) for the settings a fine-tune run
 uses, the third value of mvlt_adamw_step's mask byte in the header, and FusedAdamW's mask following requires_grad (built here from a CPU store)."""
+import json
 import os
 import re
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -28,7 +31,7 @@ def stage_prefixes(*stages):
 
 
 def plan_of(m):
-    from mvlt_amd.schedule import backward_plan
+    from mvlt_amd.plan import backward_plan
     return backward_plan(m)
 
 
@@ -169,3 +172,45 @@ def test_fused_adamw_mask_follows_requires_grad(model):
     assert not opt._all_frozen(lo, hi)
     o, n, _ = S.offsets["block1.0.norm1.bias"]
     assert opt._all_frozen(o, o + n)
+
+
+_PLAN_CHILD = """
+import json, sys
+import mvlt_amd.plan as plan
+assert not any(m in sys.modules for m in ("mvlt_amd._lib", "mvlt_amd.ops", "mvlt_amd.pvlt")), sorted(m for m in sys.modules if m.startswith("mvlt_amd"))
+spec = json.load(sys.stdin)
+
+class P:
+    def __init__(self, on):
+        self.requires_grad = on
+
+class M:
+    depths, loss_type = spec["depths"], spec["loss_type"]
+    def named_parameters(self):
+        return [(n, P(on)) for n, on in spec["params"]]
+
+print(json.dumps(plan.backward_plan(M()).signature()))
+"""
+
+
+def _child(code, stdin="", **env):
+    return subprocess.run([sys.executable, "-c", code], input=stdin, capture_output=True, text=True, cwd=ROOT, env={**os.environ, **env}, timeout=120)
+
+
+def test_plan_needs_no_library(model):
+    """a fresh process whose MVLT_HIP_LIB names no file imports mvlt_amd.plan and plans pvlt_tiny (its parameter names, flags, depths and loss types handed
+    over as data: the model classes live behind the library) -- the same plan as in this process"""
+    freeze(model, *stage_prefixes(1, 2), "text_embeddings.")
+    spec = dict(depths=list(model.depths), loss_type=dict(model.loss_type), params=[(n, p.requires_grad) for n, p in model.named_parameters()])
+    r = _child(_PLAN_CHILD, json.dumps(spec), MVLT_HIP_LIB=os.path.join(ROOT, "no", "such", "libmvlt_hip.so"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout) == json.loads(json.dumps(plan_of(model).signature()))
+    r = _child("import mvlt_amd._lib", MVLT_HIP_LIB=os.path.join(ROOT, "no", "such", "libmvlt_hip.so"))
+    assert r.returncode != 0 and "is missing" in r.stderr                     # (the variable does reach the child: the binding itself refuses)
+
+
+@pytest.mark.parametrize("module", ["schedule", "mim", "trunk", "heads"])
+def test_imports_first_in_a_fresh_process(module):
+    """no import-order dependence among the schedule's modules: each one comes up as the first mvlt_amd import of a process"""
+    r = _child(f"import mvlt_amd.{module}")
+    assert r.returncode == 0, r.stderr[-2000:]

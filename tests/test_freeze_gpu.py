@@ -1,5 +1,5 @@
 """GPU: frozen parameters (requires_grad=False) are honoured at every layer -- the third value of mvlt_adamw_step's mask byte, FusedAdamW leaving frozen
-parameters / moments / bf16 copies alone, the backward pruned to the plan of mvlt_amd.schedule.backward_plan (same gradients for what stays trainable,
+parameters / moments / bf16 copies alone, the backward pruned to the plan of mvlt_amd.plan.backward_plan (same gradients for what stays trainable,
 no launches for what does not), freeze -> un-freeze on one optimizer, the engine loop in the fine-tune shape, and two data-parallel ranks.
 The yardsticks are torch.optim.AdamW and the build's own all-trainable run on the same batch; shapes are the smallest the suite builds
 (tests/test_clip_gpu.py)."""
@@ -309,7 +309,7 @@ def test_trainable_gradients_equal_the_unfrozen_run(parity, dtype, setting):
 @contextlib.contextmanager
 def _counting(m):
     """counting closures around the weight-gradient / attention-backward / embedding-backward entries for the duration of a backward"""
-    from mvlt_amd import ops, schedule
+    from mvlt_amd import layers, ops, trunk
     S = m.store
     calls = dict(gemm_tn=0, mlp_bwd_dw=0, sr_attention_bwd=0, bert_embed_bwd=0, conv_wgrad=0)
     in_trunk = [0]
@@ -323,7 +323,7 @@ def _counting(m):
         return bool(hit) and not any(hit)
 
     saved = {k: getattr(ops, k) for k in ("gemm_tn", "mlp_bwd_dw", "sr_attention_bwd", "bert_embed_bwd")}
-    saved_cw, saved_bw = schedule.conv_wgrad, schedule.TrunkStep.backward
+    saved_cw, saved_bw = layers.conv_wgrad, trunk.TrunkStep.backward
 
     def wrap(key, fn):
         def f(*a, **k):
@@ -352,13 +352,13 @@ def _counting(m):
 
     for k, fn in saved.items():
         setattr(ops, k, wrap(k, fn))
-    schedule.conv_wgrad, schedule.TrunkStep.backward = cw, bw
+    layers.conv_wgrad, trunk.TrunkStep.backward = cw, bw
     try:
         yield calls, frozen_targets
     finally:
         for k, fn in saved.items():
             setattr(ops, k, fn)
-        schedule.conv_wgrad, schedule.TrunkStep.backward = saved_cw, saved_bw
+        layers.conv_wgrad, trunk.TrunkStep.backward = saved_cw, saved_bw
 
 
 @pytest.mark.parametrize("setting", ["all", "heads", "text", "lower", "one", "patch1", "fc2s3", "pos3"])

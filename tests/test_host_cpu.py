@@ -302,7 +302,7 @@ def _toy_store():
 
 
 class _SideEffectFn(torch.autograd.Function):
-    """the shape of schedule._TrunkFn: gradients are ADDED into the flat buffer as a side effect, the slices are returned"""
+    """the shape of trunk._TrunkFn: gradients are ADDED into the flat buffer as a side effect, the slices are returned"""
 
     @staticmethod
     def forward(ctx, x, S, val, *params):

@@ -104,7 +104,7 @@ def test_oracle_refuses_896x224_like_the_reference():
 
 
 def test_input_rule_names_both_sides():
-    from mvlt_amd.schedule import check_input_size, stage_grids
+    from mvlt_amd.plan import check_input_size, stage_grids
     m = types.SimpleNamespace(patch_size=4)
     for H, W in ((256, 192), (192, 320), (1568, 32), (224, 224)):
         check_input_size(m, H, W)

@@ -42,7 +42,7 @@ def case(B, H, N, M, dt, streamed, reps):
     f = ops.sr_attention_fwd_streamed if streamed else ops.sr_attention_fwd
     b = ops.sr_attention_bwd_streamed if streamed else ops.sr_attention_bwd
     tf = timeit(lambda: f(q, kv, o, lse, B, H, N, M, C, 2 * C, C, 0, C, 0.125), reps)
-    # the zero fill of the fp32 dKV is part of what an atomics-reducing backward costs its caller (schedule.py's pool_zeros)
+    # the zero fill of the fp32 dKV is part of what an atomics-reducing backward costs its caller (trunk.py's pool_zeros)
     tb = timeit(lambda: (dkv.zero_(), b(q, kv, o, do, lse, dq, dkv, B, H, N, M, C, 2 * C, C, 2 * C, 0, C, 0.125)), reps)
     return tf, tb
 

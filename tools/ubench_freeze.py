@@ -25,7 +25,7 @@ import bench                                   # noqa: E402
 from mvlt_amd import ops, pvlt                 # noqa: E402
 from mvlt_amd.engine import BF16Scaler, train_step      # noqa: E402
 from mvlt_amd.optim import FusedAdamW          # noqa: E402
-from mvlt_amd.schedule import backward_plan    # noqa: E402
+from mvlt_amd.plan import backward_plan    # noqa: E402
 
 EMBEDS = ("patch_embed{}", "text_embed{}", "pos_embed{}", "text_pos_embed{}")
 SETTINGS = ("all", "text", "lower", "heads")
