@@ -1,9 +1,9 @@
-/* mvlt_hip_plan.h -- what mvlt_gemm_nt / mvlt_gemm_tn WOULD launch for an argument struct, without launching it: entry points of libmvlt_hip.so added
+/* mvlt_hip_plan.h -- what mvlt_gemm_nt / mvlt_gemm_tn and the mvlt_sr_attention_* entry points WOULD launch for an argument struct, without launching it: entry points of libmvlt_hip.so added
  * beside the C ABI of mvlt_hip.h (version 8) and the additions of mvlt_hip_ext.h and mvlt_hip_ema.h, whose lists of prototypes and versions stay as they are.
  *
- * The two GEMM entry points are "plan, then launch": the plan -- argument checks, choice of kernel instantiation, launch geometry, trailing kernel
- * arguments, partial-tile bookkeeping -- is a pure host function (mvlt_amd/csrc/gemm_plan.h: no HIP call, no global state), and the entry points below
- * hand it out.  They touch no device: they run on a machine without a GPU, and tests/test_gemm_plan_cpu.py pins them against recorded launches.
+ * The GEMM and the SR-attention entry points are "plan, then launch": the plan -- argument checks, choice of kernel instantiation, launch geometry, trailing kernel
+ * arguments, partial-tile bookkeeping -- is a pure host function (mvlt_amd/csrc/gemm_plan.h, attn_plan.h: no HIP call, no global state), and the entry points below
+ * hand it out.  They touch no device: they run on a machine without a GPU, and tests/test_gemm_plan_cpu.py / tests/test_attn_plan_cpu.py pin them against recorded launches.
  * A binding compares mvlt_plan_version() with the MVLT_PLAN_VERSION it was written against (mvlt_amd/_lib.py PLAN_VERSION) before it calls anything here.
  */
 #ifndef MVLT_HIP_PLAN_H
@@ -15,8 +15,9 @@ extern "C" {
 #endif
 
 /* Version of this header: bumped whenever a signature or the struct below changes.
- *   1: mvlt_gemm_plan, mvlt_gemm_nt_plan(), mvlt_gemm_tn_plan(), mvlt_gemm_plan_name(), mvlt_gemm_plan_sizeof() */
-#define MVLT_PLAN_VERSION 1
+ *   1: mvlt_gemm_plan, mvlt_gemm_nt_plan(), mvlt_gemm_tn_plan(), mvlt_gemm_plan_name(), mvlt_gemm_plan_sizeof()
+ *   2: + mvlt_attn_plan, mvlt_sr_attention_fwd_plan(), mvlt_sr_attention_bwd_plan(), mvlt_attn_plan_name(), mvlt_attn_plan_sizeof() */
+#define MVLT_PLAN_VERSION 2
 int mvlt_plan_version(void);
 
 /* kernel families of the GEMMs (mvlt_amd/csrc/gemm_<family>.hip, dispatched by gemm.hip); tp[] holds the template arguments of the instantiation in the order the kernel declares them
@@ -57,6 +58,33 @@ int mvlt_gemm_tn_plan(const mvlt_gemm_tn_args* args, mvlt_gemm_plan* plan);
  * ("" for MVLT_GEMM_NONE).  Returns the length written, <0 when buf is too small or the family unknown. */
 int mvlt_gemm_plan_name(const mvlt_gemm_plan* plan, char* buf, size_t n);
 int mvlt_gemm_plan_sizeof(void);
+
+/* kernel families of SR-attention (mvlt_amd/csrc/attention_<family>.hip, dispatched by attention.hip); tp[] as above */
+#define MVLT_ATTN_FWD 1         /* attn_fwd_kernel<T, NKT>                  tp = {dtype, NKT}          resident forward: fp32, and bf16 past 192 keys */
+#define MVLT_ATTN_FWD2 2        /* attn_fwd2_kernel<NKT, PADDED, NW>        tp = {NKT, PADDED, NW}     resident bf16 forward up to 192 keys */
+#define MVLT_ATTN_BWD 3         /* attn_bwd_kernel<T, NW, TPW>              tp = {dtype, NW, TPW}      resident fp32 backward */
+#define MVLT_ATTN_BWD_DMA 4     /* attn_bwd_dma_kernel<NW, TPW>             tp = {NW, TPW}             resident bf16 backward */
+#define MVLT_ATTN_FWD_STREAM 5  /* attn_fwd_stream_kernel<T, KB>            tp = {dtype, KB}           key-streamed forward, any M */
+#define MVLT_ATTN_BWD_STREAM 6  /* attn_bwd_stream_kernel<T, NW, TPW>       tp = {dtype, NW, TPW}      key-streamed backward, any M */
+
+typedef struct mvlt_attn_plan {
+  int family;                /* MVLT_ATTN_* */
+  int tp[4];
+  int grid;                  /* workgroups (x) */
+  int block;
+  int lds;                   /* dynamic LDS bytes */
+  int nq_chunks;             /* query chunks per (batch, head): the kernels' first scalar argument */
+  int q_per_wg;              /* queries per chunk: their second (the streamed forward's is the constant 128 and no kernel argument) */
+} mvlt_attn_plan;
+
+/* Argument checks + choice, exactly what mvlt_sr_attention_fwd / _bwd (streamed == 0) and mvlt_sr_attention_fwd_streamed / _bwd_streamed (streamed != 0) do before they
+ * launch: same return codes, same mvlt_last_error() texts.  Pointers are tested for null, never followed.  mvlt_sr_attention_bwd_chunks() is nq_chunks of the backward plan
+ * for an fp32 dKV. */
+int mvlt_sr_attention_fwd_plan(const mvlt_attn_args* args, int streamed, mvlt_attn_plan* plan);
+int mvlt_sr_attention_bwd_plan(const mvlt_attn_bwd_args* args, int streamed, mvlt_attn_plan* plan);
+/* as mvlt_gemm_plan_name: "attn_bwd_dma_kernel<4, 3>" */
+int mvlt_attn_plan_name(const mvlt_attn_plan* plan, char* buf, size_t n);
+int mvlt_attn_plan_sizeof(void);
 
 #ifdef __cplusplus
 }

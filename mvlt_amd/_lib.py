@@ -227,7 +227,7 @@ EMA_VERSION = 1          # include/mvlt_hip_ema.h MVLT_EMA_VERSION this binding 
 if lib.mvlt_ema_version() != EMA_VERSION:
     raise ImportError(f"EMA entry points mismatch: {LIB_PATH} is version {lib.mvlt_ema_version()}, the binding is version {EMA_VERSION} (stale build? run python -m mvlt_amd.build)")
 
-# The entry points of include/mvlt_hip_plan.h (what mvlt_gemm_nt / mvlt_gemm_tn would launch, without a device): a fourth table with its own struct,
+# The entry points of include/mvlt_hip_plan.h (what the GEMM and the SR-attention entry points would launch, without a device): a fourth table with its own structs,
 # bound and version-checked like the ones above (tests/test_gemm_plan_cpu.py compares both with that header).
 class GemmPlan(C.Structure):
     _fields_ = [("family", c_int), ("tp", c_int * 6), ("grid", c_int * 3), ("block", c_int), ("lds", c_int),
@@ -235,13 +235,21 @@ class GemmPlan(C.Structure):
                 ("swap_operands", c_int), ("fold", c_int), ("fold_grid", c_int), ("partials_need", c_long)]
 
 
-PLAN_STRUCTS = (("mvlt_gemm_plan", GemmPlan),)
+class AttnPlan(C.Structure):
+    _fields_ = [("family", c_int), ("tp", c_int * 4), ("grid", c_int), ("block", c_int), ("lds", c_int), ("nq_chunks", c_int), ("q_per_wg", c_int)]
+
+
+PLAN_STRUCTS = (("mvlt_gemm_plan", GemmPlan), ("mvlt_attn_plan", AttnPlan))
 PLAN_PROTOTYPES = {
     "mvlt_plan_version": (_i, []),
     "mvlt_gemm_nt_plan": (_i, [C.POINTER(GemmNTArgs), C.POINTER(GemmPlan)]),
     "mvlt_gemm_tn_plan": (_i, [C.POINTER(GemmTNArgs), C.POINTER(GemmPlan)]),
     "mvlt_gemm_plan_name": (_i, [C.POINTER(GemmPlan), _str, C.c_size_t]),
     "mvlt_gemm_plan_sizeof": (_i, []),
+    "mvlt_sr_attention_fwd_plan": (_i, [C.POINTER(AttnArgs), _i, C.POINTER(AttnPlan)]),
+    "mvlt_sr_attention_bwd_plan": (_i, [C.POINTER(AttnBwdArgs), _i, C.POINTER(AttnPlan)]),
+    "mvlt_attn_plan_name": (_i, [C.POINTER(AttnPlan), _str, C.c_size_t]),
+    "mvlt_attn_plan_sizeof": (_i, []),
 }
 for _name, (_res, _args) in PLAN_PROTOTYPES.items():
     if not hasattr(lib, _name):
@@ -249,10 +257,11 @@ for _name, (_res, _args) in PLAN_PROTOTYPES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
-PLAN_VERSION = 1         # include/mvlt_hip_plan.h MVLT_PLAN_VERSION this binding was written against
-if lib.mvlt_plan_version() != PLAN_VERSION or lib.mvlt_gemm_plan_sizeof() != C.sizeof(GemmPlan):
-    raise ImportError(f"GEMM plan entry points mismatch: {LIB_PATH} is version {lib.mvlt_plan_version()} with a {lib.mvlt_gemm_plan_sizeof()}-byte mvlt_gemm_plan, the binding is "
-                      f"version {PLAN_VERSION} with {C.sizeof(GemmPlan)} bytes (stale build? run python -m mvlt_amd.build)")
+PLAN_VERSION = 2         # include/mvlt_hip_plan.h MVLT_PLAN_VERSION this binding was written against
+if lib.mvlt_plan_version() != PLAN_VERSION or lib.mvlt_gemm_plan_sizeof() != C.sizeof(GemmPlan) or lib.mvlt_attn_plan_sizeof() != C.sizeof(AttnPlan):
+    raise ImportError(f"plan entry points mismatch: {LIB_PATH} is version {lib.mvlt_plan_version()} with a {lib.mvlt_gemm_plan_sizeof()}-byte mvlt_gemm_plan and a "
+                      f"{lib.mvlt_attn_plan_sizeof()}-byte mvlt_attn_plan, the binding is version {PLAN_VERSION} with {C.sizeof(GemmPlan)} and {C.sizeof(AttnPlan)} bytes "
+                      f"(stale build? run python -m mvlt_amd.build)")
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 

@@ -6,19 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/mvlt_hip_plan.h"
-
-#ifndef MVLT_OK                 // (common.h has them for the HIP translation units)
-#define MVLT_OK 0
-#define MVLT_ERR_ARG -1
-void mvlt_set_error(const char* fmt, ...);
-#define MVLT_REQUIRE(cond, ...)                 \
-  do {                                          \
-    if (!(cond)) {                              \
-      mvlt_set_error(__VA_ARGS__);              \
-      return MVLT_ERR_ARG;                      \
-    }                                           \
-  } while (0)
-#endif
+#include "plan_common.h"        // MVLT_REQUIRE and the return codes where common.h is not there
 #ifndef MVLT_NT_EARLY_DEFAULT
 #define MVLT_NT_EARLY_DEFAULT 0x100  // early slot release in the NT K-loop: logits GEMM 172 -> 163 us, step -0.16 ms (same-box A/B, MVLT_NT_EARLY=0 / 1)
 #endif

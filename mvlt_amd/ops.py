@@ -47,12 +47,12 @@ def gemm_nt(A, B, C_out, *dims, **kw):
 
 
 class Plan:
-    """what a GEMM call would launch (mvlt_gemm_plan of include/mvlt_hip_plan.h): .name is the kernel as _lib.last_kernel() prints it, .p the struct"""
+    """what a GEMM or attention call would launch (mvlt_gemm_plan / mvlt_attn_plan of include/mvlt_hip_plan.h): .name is the kernel as _lib.last_kernel() prints it, .p the struct"""
 
-    def __init__(self, plan_fn, args):
-        p, buf = L.GemmPlan(), C.create_string_buffer(256)
-        check(plan_fn(C.byref(args), C.byref(p)), "mvlt_gemm_plan")
-        check(min(L.lib.mvlt_gemm_plan_name(C.byref(p), buf, len(buf)), 0), "mvlt_gemm_plan_name")
+    def __init__(self, plan_fn, args, cls=None, name_fn=None):
+        p, buf = (cls or L.GemmPlan)(), C.create_string_buffer(256)
+        check(plan_fn(C.byref(args), C.byref(p)), "plan")
+        check(min((name_fn or L.lib.mvlt_gemm_plan_name)(C.byref(p), buf, len(buf)), 0), "plan name")
         self.p, self.name = p, buf.value.decode()
 
     def __getattr__(self, field):
@@ -176,20 +176,35 @@ def batch_sum(x, out, B, R, Cdim, batch_stride_rows, ld, acc2=None, split=0):
     return out
 
 
-def _attention_fwd(entry, Q, KV, O, lse, B, H, N, M, ldq, ldkv, ldo, k_off, v_off, scale):
+def _attention_fwd_args(Q, KV, O, lse, B, H, N, M, ldq, ldkv, ldo, k_off, v_off, scale):
     assert Q.dtype == KV.dtype == O.dtype and Q.dtype in DT
-    a = L.AttnArgs(Q=ptr(Q), KV=ptr(KV), O=ptr(O), lse=ptr(lse), B=B, H=H, N=N, M=M, ldq=ldq, ldkv=ldkv, ldo=ldo, k_off=k_off, v_off=v_off,
-                   scale=scale, dtype=DT[Q.dtype])
-    check(getattr(L.lib, entry)(C.byref(a), stream_ptr()), entry)
-    return O
+    return L.AttnArgs(Q=ptr(Q), KV=ptr(KV), O=ptr(O), lse=ptr(lse), B=B, H=H, N=N, M=M, ldq=ldq, ldkv=ldkv, ldo=ldo, k_off=k_off, v_off=v_off,
+                      scale=scale, dtype=DT[Q.dtype])
 
 
-def _attention_bwd(entry, Q, KV, O, dO, lse, dQ, dKV, B, H, N, M, ldq, ldkv, ldo, lddkv, k_off, v_off, scale):
+def _attention_bwd_args(Q, KV, O, dO, lse, dQ, dKV, B, H, N, M, ldq, ldkv, ldo, lddkv, k_off, v_off, scale):
     assert dKV.dtype == torch.float32 or (dKV.dtype == torch.bfloat16 and Q.dtype == torch.bfloat16)
-    a = L.AttnBwdArgs(Q=ptr(Q), KV=ptr(KV), O=ptr(O), dO=ptr(dO), lse=ptr(lse), dQ=ptr(dQ), dKV=ptr(dKV), B=B, H=H, N=N, M=M,
-                      ldq=ldq, ldkv=ldkv, ldo=ldo, lddkv=lddkv, k_off=k_off, v_off=v_off, scale=scale, dtype=DT[Q.dtype], dkv_dtype=DT[dKV.dtype])
-    check(getattr(L.lib, entry)(C.byref(a), stream_ptr()), entry)
-    return dQ, dKV
+    return L.AttnBwdArgs(Q=ptr(Q), KV=ptr(KV), O=ptr(O), dO=ptr(dO), lse=ptr(lse), dQ=ptr(dQ), dKV=ptr(dKV), B=B, H=H, N=N, M=M,
+                         ldq=ldq, ldkv=ldkv, ldo=ldo, lddkv=lddkv, k_off=k_off, v_off=v_off, scale=scale, dtype=DT[Q.dtype], dkv_dtype=DT[dKV.dtype])
+
+
+def _attention_fwd(entry, *args):
+    check(getattr(L.lib, entry)(C.byref(_attention_fwd_args(*args)), stream_ptr()), entry)
+    return args[2]
+
+
+def _attention_bwd(entry, *args):
+    check(getattr(L.lib, entry)(C.byref(_attention_bwd_args(*args)), stream_ptr()), entry)
+    return args[5], args[6]
+
+
+def attention_plan(*args, streamed=False):
+    """what sr_attention_fwd (14 arguments) / sr_attention_bwd (18 arguments) or, with streamed=True, their *_streamed forms would launch for the same arguments
+    (mvlt_attn_plan of include/mvlt_hip_plan.h, .name as _lib.last_kernel() prints it); nothing is launched"""
+    fwd = len(args) == 14
+    a = (_attention_fwd_args if fwd else _attention_bwd_args)(*args)
+    plan_fn = L.lib.mvlt_sr_attention_fwd_plan if fwd else L.lib.mvlt_sr_attention_bwd_plan
+    return Plan(lambda args_ref, plan_ref: plan_fn(args_ref, int(streamed), plan_ref), a, L.AttnPlan, L.lib.mvlt_attn_plan_name)
 
 
 def sr_attention_fwd(Q, KV, O, lse, B, H, N, M, ldq, ldkv, ldo, k_off, v_off, scale):

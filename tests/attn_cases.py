@@ -30,7 +30,7 @@ REPEL = 256.0
 SCALE = 0.125
 VMAX = 3                      # bound of |V|, |dO| and the free key dims
 
-# both sides of every rung of every dispatch ladder of csrc/attention.hip (32-key tiles of the forwards, the <NW,TPW> ladder of the
+# both sides of every rung of every dispatch ladder of csrc/attn_plan.h (32-key tiles of the forwards, the <NW,TPW> ladder of the
 # backward at 64 / 128 / 192 / 256 / 288 / 320, the resident ranges' ends 288 (fp32) and 320 (bf16), past one streamed key block)
 LADDER_M = [1, 31, 32, 33, 64, 65, 96, 97, 128, 129, 160, 161, 192, 193, 224, 225, 256, 257, 288, 289, 320, 321, 385]
 # every M at which the GPU tests use decisive inputs: test_attention_cases_cpu.py pins the premises for each

@@ -1,4 +1,4 @@
-"""GPU: the SR-attention kernels (csrc/attention.hip) on inputs that make single keys decisive, at both sides of every rung of every
+"""GPU: the SR-attention kernels (csrc/attention_<family>.hip, dispatched by csrc/attn_plan.h) on inputs that make single keys decisive, at both sides of every rung of every
 dispatch ladder, through strided layouts with guards, and at the numeric edges -- against the float64 reference of tests/attn_cases.py
 (softmax(Q K^T scale) V and its autograd from the operands as the kernel reads them).  The inputs' premises are pinned on the CPU by
 tests/test_attention_cases_cpu.py.
@@ -19,18 +19,21 @@ Instantiation -> the case that launches it and asserts its name (mvlt_amd._lib.l
       <1,true> M 1, 31   <1,false> 32   <2,true> 33   <2,false> 64   <3,true> 65   <3,false> 96   <4,true> 97   <4,false> 128
       <5,true> 129       <5,false> 160  <6,true> 161  <6,false> 192
   attn_fwd_kernel<bf16, NKT>        bf16 public forward, 193 <= M <= 320
-      <7> 193, 224   <8> 225, 256   <9> 257, 288   <10> 289, 320          (NKT <= 6 is unreachable in bf16: attn_fwd2_kernel takes it)
+      <7> 193, 224   <8> 225, 256   <9> 257, 288   <10> 289, 320          (NKT <= 6 is not instantiated in bf16: attn_fwd2_kernel takes it)
   attn_fwd_kernel<float, NKT>       fp32 public forward, M <= 288
       <1> 1, 31, 32   <2> 33, 64   <3> 65, 96   <4> 97, 128   <5> 129, 160   <6> 161, 192   <7> 193, 224   <8> 225, 256   <9> 257, 288
-      (<float, 10> is compiled but unreachable: fp32 M > 288 streams)
+      (<float, 10> is not instantiated: fp32 M > 288 streams)
   attn_bwd_dma_kernel<NW, TPW>      bf16 public backward, M <= 320
       <4,1> 1..64   <4,2> 65..128   <4,3> 129..192   <8,2> 193..256   <6,3> 257, 288   <8,3> 289, 320
   attn_bwd_kernel<float, NW, TPW>   fp32 public backward, M <= 288
-      <4,1> 1..64   <4,2> 65..128   <4,3> 129..192   <8,2> 193..256   <6,3> 257, 288      (<float, 8, 3> is unreachable: fp32 M > 288 streams)
+      <4,1> 1..64   <4,2> 65..128   <4,3> 129..192   <8,2> 193..256   <6,3> 257, 288      (<float, 8, 3> is not instantiated: fp32 M > 288 streams)
   attn_fwd_stream_kernel<bf16, 128> / attn_bwd_stream_kernel<bf16, 4, 2>     bf16 public M 321, 385; the *_streamed exports at every M
   attn_fwd_stream_kernel<float, 64> / attn_bwd_stream_kernel<float, 4, 1>    fp32 public M 289, 320, 321, 385; the *_streamed exports at every M
+The tables below (expected_fwd, expected_bwd, bwd_ladder) are the independent statement of the ladders; run() also asks the library's own plan
+(ops.attention_plan, no launch) and holds it to the kernel that ran.  tests/test_attn_plan_cpu.py checks the plan at every M without a GPU.
 """
 import math
+import re
 import types
 
 import pytest
@@ -108,6 +111,18 @@ def ran(expected):
         assert name == want, f"meant to reach {want}, the library launched {name}"
 
 
+def planned(plan):
+    """the instantiation a plan names (ops.attention_plan(...).name: demangled text, or the mangled name of an instantiation over bf16) as ran() takes it"""
+    name = plan.name
+    if name.startswith("_Z"):
+        base, enc = re.fullmatch(r"_ZN12_GLOBAL__N_1\d+([a-z_0-9]+?)I(.*)EEv\d+mvlt_\w+", name).groups()
+        targs = tuple(BF if t == "DF16b" else F32 if t == "f" else bool(int(t[2:-1])) if t[1] == "b" else int(t[2:-1]) for t in re.findall(r"DF16b|f|L[ib]\d+E", enc))
+    else:
+        base, txt = re.fullmatch(r"(\w+)<(.*)>", name).groups()
+        targs = tuple(F32 if t == "float" else t == "true" if t in ("true", "false") else int(t) for t in txt.split(", "))
+    return base, targs
+
+
 # ------------------------------------------------------------------------------------------------ layouts, buffers, guards
 def contiguous(C):
     """the schedule's layout"""
@@ -168,9 +183,10 @@ def run(ops, case, streamed=False, layout=None, forward=True, backward=True, dkv
     o = lse = None
     if forward:
         o, lse = Buf(io, dt, L.ldo), Buf(ilse, F32, 1)
-        (ops.sr_attention_fwd_streamed if streamed else ops.sr_attention_fwd)(
-            q.t[L.q_col0:], kv.t, o.t, lse.t, B, H, N, M, L.ldq, L.ldkv, L.ldo, L.k_off, L.v_off, case.scale)
+        fwd_args = (q.t[L.q_col0:], kv.t, o.t, lse.t, B, H, N, M, L.ldq, L.ldkv, L.ldo, L.k_off, L.v_off, case.scale)
+        (ops.sr_attention_fwd_streamed if streamed else ops.sr_attention_fwd)(*fwd_args)
         ran(expected_fwd(M, dt, streamed))
+        ran(planned(ops.attention_plan(*fwd_args, streamed=streamed)))
         torch.cuda.synchronize()
         for b, n in ((o, "O"), (lse, "lse"), (q, "Q"), (kv, "KV")):
             b.check_sentinels(f"{what} forward, {n}")
@@ -180,9 +196,10 @@ def run(ops, case, streamed=False, layout=None, forward=True, backward=True, dkv
             o, lse = Buf(io, dt, L.ldo, case.ref[0]), Buf(ilse, F32, 1, case.ref[1])
         do = Buf(io, dt, 0, case.do)
         dq, dkv = Buf(iq, dt, L.ldq), Buf(idkv, F32, L.lddkv, live=dkv_fill)
-        (ops.sr_attention_bwd_streamed if streamed else ops.sr_attention_bwd)(
-            q.t[L.q_col0:], kv.t, o.t, do.t, lse.t, dq.t[L.q_col0:], dkv.t, B, H, N, M, L.ldq, L.ldkv, L.ldo, L.lddkv, L.k_off, L.v_off, case.scale)
+        bwd_args = (q.t[L.q_col0:], kv.t, o.t, do.t, lse.t, dq.t[L.q_col0:], dkv.t, B, H, N, M, L.ldq, L.ldkv, L.ldo, L.lddkv, L.k_off, L.v_off, case.scale)
+        (ops.sr_attention_bwd_streamed if streamed else ops.sr_attention_bwd)(*bwd_args)
         ran(expected_bwd(M, dt, streamed))
+        ran(planned(ops.attention_plan(*bwd_args, streamed=streamed)))
         torch.cuda.synchronize()
         for b, n in ((dq, "dQ"), (dkv, "dKV"), (o, "O"), (lse, "lse"), (do, "dO"), (q, "Q"), (kv, "KV")):
             b.check_sentinels(f"{what} backward, {n}")

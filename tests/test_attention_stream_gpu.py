@@ -1,4 +1,4 @@
-"""GPU: the key-streamed SR-attention kernels (csrc/attention.hip: attn_fwd_stream_kernel / attn_bwd_stream_kernel) against a plain
+"""GPU: the key-streamed SR-attention kernels (csrc/attention_stream.hip: attn_fwd_stream_kernel / attn_bwd_stream_kernel; routed by csrc/attn_plan.h) against a plain
 PyTorch fp32 reference -- through the public entry points past the LDS-resident range (bf16 M > 320 keys, fp32 M > 288), and through
 the streamed exports at small M, next to the resident kernels on the same data.
 Tolerances as tests/test_kernels_gpu.py: forward 2e-2 (bf16) / 1e-3 (fp32) max-relative, lse 2e-2 / 1e-3 absolute, dQ / dKV 3e-2 / 2e-3."""

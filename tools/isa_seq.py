@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instruction-class SEQUENCE of the MFMA-heaviest loop of one kernel (hipcc -S output, no GPU needed): how the compiler ordered matrix, VALU,
 LDS and wait instructions -- M mfma, E transcendental, v other VALU, r LDS read, w LDS write, g global / buffer, | s_waitcnt, B s_barrier, s SALU.
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -S --cuda-device-only mvlt_amd/csrc/attention.hip -o /tmp/attn.s
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -S --cuda-device-only mvlt_amd/csrc/attention_bwd_dma.hip -o /tmp/attn.s
     python tools/isa_seq.py /tmp/attn.s attn_bwd_dma_kernelILi4ELi3E"""
 import re
 import sys

@@ -1,4 +1,4 @@
-"""Key-streamed SR-attention microbench (csrc/attention.hip: attn_fwd_stream_kernel / attn_bwd_stream_kernel).
+"""Key-streamed SR-attention microbench (csrc/attention_stream.hip: attn_fwd_stream_kernel / attn_bwd_stream_kernel).
 
 1. The four stage shapes of pvlt_tiny at 512 px, T = 128, batch 32 (every stage sees M = 384 keys): the streamed forward and backward
    through the public entry points, with the fraction of MFMA peak (bf16 2.5 PF dense, fp32 157 TF).
