@@ -390,7 +390,8 @@ def test_gemm_nt_conv3x3_gather(ops, dtype, h, w, Cin, Cout, variant, fam_bf, fa
 
 @pytest.mark.parametrize("N,K,M,odt", [(64, 72, 257, F32), (128, 200, 257, F32), (64, 72, 130, BF)])
 def test_gemm_nt_layernorm_epilogue_c_part(ops, N, K, M, odt):
-    """post_y: the C / R part of the LayerNorm epilogue is the residual epilogue and exact; the normalised rows stay with the tolerance test"""
+    """post_y: the C / R part of the LayerNorm epilogue is the residual epilogue and exact; the normalised rows and their statistics are checked against a
+    float64 reference on exactly known rows, with per-row bars and guards, by tests/test_fusedln_edges_gpu.py (test_gemm_layernorm_epilogue)"""
     A, W, bias = ints((M, K), -3, 3, BF, 26), ints((N, K), -3, 3, BF, 27), ints(N, -9, 9, F32, 28)
     rps = M // 2 - 3
     scale = picks((M + rps - 1) // rps, [0.0, 0.5, 1.0, 2.0], 29)
