@@ -1,9 +1,9 @@
-/* mvlt_hip_plan.h -- what mvlt_gemm_nt / mvlt_gemm_tn and the mvlt_sr_attention_* entry points WOULD launch for an argument struct, without launching it: entry points of libmvlt_hip.so added
+/* mvlt_hip_plan.h -- what mvlt_gemm_nt / mvlt_gemm_tn, the mvlt_sr_attention_* and the mvlt_mlp_* entry points WOULD launch for an argument struct, without launching it: entry points of libmvlt_hip.so added
  * beside the C ABI of mvlt_hip.h (version 8) and the additions of mvlt_hip_ext.h and mvlt_hip_ema.h, whose lists of prototypes and versions stay as they are.
  *
- * The GEMM and the SR-attention entry points are "plan, then launch": the plan -- argument checks, choice of kernel instantiation, launch geometry, trailing kernel
- * arguments, partial-tile bookkeeping -- is a pure host function (mvlt_amd/csrc/gemm_plan.h, attn_plan.h: no HIP call, no global state), and the entry points below
- * hand it out.  They touch no device: they run on a machine without a GPU, and tests/test_gemm_plan_cpu.py / tests/test_attn_plan_cpu.py pin them against recorded launches.
+ * The GEMM, the SR-attention and the fused-MLP entry points are "plan, then launch": the plan -- argument checks, choice of kernel instantiation, launch geometry, trailing kernel
+ * arguments, partial-tile bookkeeping -- is a pure host function (mvlt_amd/csrc/gemm_plan.h, attn_plan.h, mlp_plan.h: no HIP call, no global state), and the entry points below
+ * hand it out.  They touch no device: they run on a machine without a GPU, and tests/test_gemm_plan_cpu.py / tests/test_attn_plan_cpu.py / tests/test_mlp_plan_cpu.py pin them against recorded launches.
  * A binding compares mvlt_plan_version() with the MVLT_PLAN_VERSION it was written against (mvlt_amd/_lib.py PLAN_VERSION) before it calls anything here.
  */
 #ifndef MVLT_HIP_PLAN_H
@@ -16,8 +16,9 @@ extern "C" {
 
 /* Version of this header: bumped whenever a signature or the struct below changes.
  *   1: mvlt_gemm_plan, mvlt_gemm_nt_plan(), mvlt_gemm_tn_plan(), mvlt_gemm_plan_name(), mvlt_gemm_plan_sizeof()
- *   2: + mvlt_attn_plan, mvlt_sr_attention_fwd_plan(), mvlt_sr_attention_bwd_plan(), mvlt_attn_plan_name(), mvlt_attn_plan_sizeof() */
-#define MVLT_PLAN_VERSION 2
+ *   2: + mvlt_attn_plan, mvlt_sr_attention_fwd_plan(), mvlt_sr_attention_bwd_plan(), mvlt_attn_plan_name(), mvlt_attn_plan_sizeof()
+ *   3: + mvlt_mlp_plan, mvlt_mlp_fwd_plan(), mvlt_mlp_bwd_dx_plan(), mvlt_mlp_bwd_dw_plan(), mvlt_mlp_plan_name(), mvlt_mlp_plan_sizeof() */
+#define MVLT_PLAN_VERSION 3
 int mvlt_plan_version(void);
 
 /* kernel families of the GEMMs (mvlt_amd/csrc/gemm_<family>.hip, dispatched by gemm.hip); tp[] holds the template arguments of the instantiation in the order the kernel declares them
@@ -85,6 +86,39 @@ int mvlt_sr_attention_bwd_plan(const mvlt_attn_bwd_args* args, int streamed, mvl
 /* as mvlt_gemm_plan_name: "attn_bwd_dma_kernel<4, 3>" */
 int mvlt_attn_plan_name(const mvlt_attn_plan* plan, char* buf, size_t n);
 int mvlt_attn_plan_sizeof(void);
+
+/* kernel families of the fused MLP of stages 1-2 (mvlt_amd/csrc/mlp_<family>.hip, dispatched by mlp.hip); tp[] as above */
+#define MVLT_MLP_NONE 0         /* M <= 0: nothing to launch */
+#define MVLT_MLP_FUSED 1        /* mlp_fused_kernel<C, MODE>                tp = {C, MODE}             forward (MODE 0) / input gradient (1) with a pre-activation output or hid == 64 */
+#define MVLT_MLP_PIPE 2         /* mlp_pipe_kernel<C, MODE>                 tp = {C, MODE}             software-pipelined forward / input gradient: every other launch */
+#define MVLT_MLP_WGRAD 3        /* mlp_wgrad_kernel<C>                      tp = {C}                   weight gradients, DropPath factor per row (rows_per_scale no multiple of 64) */
+#define MVLT_MLP_WGRAD2 4       /* mlp_wgrad2_kernel<C, NW>                 tp = {C, NW}               weight gradients, factor per 64-token tile (or none) */
+
+typedef struct mvlt_mlp_plan {
+  int family;                /* MVLT_MLP_* */
+  int tp[2];
+  int grid;                  /* workgroups (x) */
+  int block;
+  int lds;                   /* dynamic LDS bytes */
+  /* the weight-gradient launches (0 elsewhere): the scalar kernel arguments behind the argument struct ... */
+  int m_per_split;           /* token rows per split: whole 64-token tiles */
+  int splits;                /* token splits */
+  int ny;                    /* 128-unit blocks of the hidden dimension */
+  /* ... and where dW1 / dW2 leave to */
+  int fold;                  /* WGRAD2.  1: the splits store bf16 partial tiles to the caller's scratch and two ordered folds add them to dw1 / dw2;  0: fp32 atomics */
+  int fold_grid[2];          /* workgroups of those folds (256 threads each); 0 without them */
+  long partials_need;        /* WGRAD2: bytes of mvlt_mlp_args.partials the partial tiles of both gradients take, 2 * splits * hid * C * 2 */
+} mvlt_mlp_plan;
+
+/* Argument checks + choice, exactly what mvlt_mlp_fwd / mvlt_mlp_bwd_dx / mvlt_mlp_bwd_dw do before they launch: same return codes, same mvlt_last_error() texts.  Pointers
+ * are looked at (null or not, low four address bits), never followed.  Beyond what the launching entry points refused before this header's version 3: a plan whose dynamic
+ * LDS exceeds 160 KB or whose grid exceeds INT_MAX is MVLT_ERR_ARG with a text naming the size. */
+int mvlt_mlp_fwd_plan(const mvlt_mlp_args* args, mvlt_mlp_plan* plan);
+int mvlt_mlp_bwd_dx_plan(const mvlt_mlp_args* args, mvlt_mlp_plan* plan);
+int mvlt_mlp_bwd_dw_plan(const mvlt_mlp_args* args, mvlt_mlp_plan* plan);
+/* as mvlt_gemm_plan_name: "mlp_wgrad2_kernel<64, 4>" ("" for MVLT_MLP_NONE) */
+int mvlt_mlp_plan_name(const mvlt_mlp_plan* plan, char* buf, size_t n);
+int mvlt_mlp_plan_sizeof(void);
 
 #ifdef __cplusplus
 }

@@ -161,7 +161,7 @@ PROTOTYPES = {
     "mvlt_head_grad_prep": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "mvlt_transpose_cast": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlt_weight_prep": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp]),          # descs: a DEVICE table of PrepDesc, hence no POINTER(PrepDesc)
-    # csrc/mlp.hip
+    # csrc/mlp.hip (kernels: csrc/mlp_<family>.hip)
     "mvlt_mlp_fwd": _by_args(MlpArgs),
     "mvlt_mlp_bwd_dx": _by_args(MlpArgs),
     "mvlt_mlp_bwd_dw": _by_args(MlpArgs),
@@ -227,7 +227,7 @@ EMA_VERSION = 1          # include/mvlt_hip_ema.h MVLT_EMA_VERSION this binding 
 if lib.mvlt_ema_version() != EMA_VERSION:
     raise ImportError(f"EMA entry points mismatch: {LIB_PATH} is version {lib.mvlt_ema_version()}, the binding is version {EMA_VERSION} (stale build? run python -m mvlt_amd.build)")
 
-# The entry points of include/mvlt_hip_plan.h (what the GEMM and the SR-attention entry points would launch, without a device): a fourth table with its own structs,
+# The entry points of include/mvlt_hip_plan.h (what the GEMM, the SR-attention and the fused-MLP entry points would launch, without a device): a fourth table with its own structs,
 # bound and version-checked like the ones above (tests/test_gemm_plan_cpu.py compares both with that header).
 class GemmPlan(C.Structure):
     _fields_ = [("family", c_int), ("tp", c_int * 6), ("grid", c_int * 3), ("block", c_int), ("lds", c_int),
@@ -239,7 +239,12 @@ class AttnPlan(C.Structure):
     _fields_ = [("family", c_int), ("tp", c_int * 4), ("grid", c_int), ("block", c_int), ("lds", c_int), ("nq_chunks", c_int), ("q_per_wg", c_int)]
 
 
-PLAN_STRUCTS = (("mvlt_gemm_plan", GemmPlan), ("mvlt_attn_plan", AttnPlan))
+class MlpPlan(C.Structure):
+    _fields_ = [("family", c_int), ("tp", c_int * 2), ("grid", c_int), ("block", c_int), ("lds", c_int), ("m_per_split", c_int), ("splits", c_int), ("ny", c_int),
+                ("fold", c_int), ("fold_grid", c_int * 2), ("partials_need", c_long)]
+
+
+PLAN_STRUCTS = (("mvlt_gemm_plan", GemmPlan), ("mvlt_attn_plan", AttnPlan), ("mvlt_mlp_plan", MlpPlan))
 PLAN_PROTOTYPES = {
     "mvlt_plan_version": (_i, []),
     "mvlt_gemm_nt_plan": (_i, [C.POINTER(GemmNTArgs), C.POINTER(GemmPlan)]),
@@ -250,6 +255,11 @@ PLAN_PROTOTYPES = {
     "mvlt_sr_attention_bwd_plan": (_i, [C.POINTER(AttnBwdArgs), _i, C.POINTER(AttnPlan)]),
     "mvlt_attn_plan_name": (_i, [C.POINTER(AttnPlan), _str, C.c_size_t]),
     "mvlt_attn_plan_sizeof": (_i, []),
+    "mvlt_mlp_fwd_plan": (_i, [C.POINTER(MlpArgs), C.POINTER(MlpPlan)]),
+    "mvlt_mlp_bwd_dx_plan": (_i, [C.POINTER(MlpArgs), C.POINTER(MlpPlan)]),
+    "mvlt_mlp_bwd_dw_plan": (_i, [C.POINTER(MlpArgs), C.POINTER(MlpPlan)]),
+    "mvlt_mlp_plan_name": (_i, [C.POINTER(MlpPlan), _str, C.c_size_t]),
+    "mvlt_mlp_plan_sizeof": (_i, []),
 }
 for _name, (_res, _args) in PLAN_PROTOTYPES.items():
     if not hasattr(lib, _name):
@@ -257,11 +267,11 @@ for _name, (_res, _args) in PLAN_PROTOTYPES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
 
-PLAN_VERSION = 2         # include/mvlt_hip_plan.h MVLT_PLAN_VERSION this binding was written against
-if lib.mvlt_plan_version() != PLAN_VERSION or lib.mvlt_gemm_plan_sizeof() != C.sizeof(GemmPlan) or lib.mvlt_attn_plan_sizeof() != C.sizeof(AttnPlan):
-    raise ImportError(f"plan entry points mismatch: {LIB_PATH} is version {lib.mvlt_plan_version()} with a {lib.mvlt_gemm_plan_sizeof()}-byte mvlt_gemm_plan and a "
-                      f"{lib.mvlt_attn_plan_sizeof()}-byte mvlt_attn_plan, the binding is version {PLAN_VERSION} with {C.sizeof(GemmPlan)} and {C.sizeof(AttnPlan)} bytes "
-                      f"(stale build? run python -m mvlt_amd.build)")
+PLAN_VERSION = 3         # include/mvlt_hip_plan.h MVLT_PLAN_VERSION this binding was written against
+_plan_sizes = [(n, getattr(lib, n + "_sizeof")(), C.sizeof(c)) for n, c in PLAN_STRUCTS]
+if lib.mvlt_plan_version() != PLAN_VERSION or any(have != want for _, have, want in _plan_sizes):
+    raise ImportError(f"plan entry points mismatch: {LIB_PATH} is version {lib.mvlt_plan_version()}, the binding is version {PLAN_VERSION}; (struct, bytes in the library, "
+                      f"bytes in the binding): {_plan_sizes} (stale build? run python -m mvlt_amd.build)")
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 

@@ -13,10 +13,10 @@ OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libmvlt_hip.so")
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result"]
-# mlp.hip: the software-pipelined kernels interleave scalar-f32 activation code with MFMAs; hipcc's SLP vectoriser would pair it into
+# the fused-MLP kernel files: the software-pipelined kernels interleave scalar-f32 activation code with MFMAs; hipcc's SLP vectoriser would pair it into
 # v_pk_*_f32 again, and packed fp32 VALU does not overlap with MFMA on gfx950 (tools/probes/valu_rates.hip: 16 x {mfma + 4 v_pk_fma} runs
 # at exactly the sum of the two, 16 x {mfma + 8 v_fma} hides half of the MFMA time)
-EXTRA = {"mlp.hip": ["-fno-slp-vectorize"]}
+EXTRA = {f: ["-fno-slp-vectorize"] for f in ("mlp_fused.hip", "mlp_pipe.hip", "mlp_wgrad.hip")}
 
 
 def _sources():

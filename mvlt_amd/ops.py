@@ -47,7 +47,7 @@ def gemm_nt(A, B, C_out, *dims, **kw):
 
 
 class Plan:
-    """what a GEMM or attention call would launch (mvlt_gemm_plan / mvlt_attn_plan of include/mvlt_hip_plan.h): .name is the kernel as _lib.last_kernel() prints it, .p the struct"""
+    """what a GEMM, attention or fused-MLP call would launch (mvlt_gemm_plan / mvlt_attn_plan / mvlt_mlp_plan of include/mvlt_hip_plan.h): .name is the kernel as _lib.last_kernel() prints it, .p the struct"""
 
     def __init__(self, plan_fn, args, cls=None, name_fn=None):
         p, buf = (cls or L.GemmPlan)(), C.create_string_buffer(256)
@@ -452,12 +452,9 @@ def upsample_l1_bwd(x, ldx, B, H, W, Cdim, scale, target, gscale, dx, lddx):
           "mvlt_upsample_l1_bwd")
 
 
-# ------------------------------------------------------------------ fused MLP (csrc/mlp.hip), bf16, C in {64, 128}
-def mlp_fwd(x, w1, b1, w2, b2, residual, out, M, Cdim, hid, *, row_scale=None, rows_per_scale=0, h_out=None, ln=None, out_op=None, post_ln=None):
-    """ln = (gamma, beta, eps, y, mean, rstd): LayerNorm(residual) folded into the operand load -- `x` is then not read (may be None);
-    y (bf16 [M, C]) receives the normalised rows, mean / rstd (fp32 [M]) the row statistics.
-    out_op: optional bf16 [M, C] copy of the output; `out` (fp32) may be None when only the copy is wanted.
-    post_ln = (gamma, beta, eps, y, mean, rstd): LayerNorm of the OUTPUT rows (the next block's norm1) from the epilogue."""
+# ------------------------------------------------------------------ fused MLP (csrc/mlp.hip, kernels in csrc/mlp_<family>.hip), bf16, C in {64, 128}
+def _mlp_fwd_args(x, w1, b1, w2, b2, residual, out, M, Cdim, hid, *, row_scale=None, rows_per_scale=0, h_out=None, ln=None, out_op=None, post_ln=None):
+    """the mvlt_mlp_args of a mlp_fwd / mlp_plan("fwd", ...) call"""
     assert w1.dtype == torch.bfloat16 and w2.dtype == torch.bfloat16
     assert residual.dtype == torch.float32 and residual.is_contiguous() and (out is not None or out_op is not None)
     assert out is None or out.dtype == torch.float32
@@ -474,32 +471,49 @@ def mlp_fwd(x, w1, b1, w2, b2, residual, out, M, Cdim, hid, *, row_scale=None, r
         pg, pb, peps, py, pm, pr = post_ln
         assert pg.dtype == pb.dtype == pm.dtype == pr.dtype == torch.float32 and py.dtype == torch.bfloat16 and py.is_contiguous()
         a.post_gamma, a.post_beta, a.post_eps, a.post_y, a.post_mean, a.post_rstd = ptr(pg), ptr(pb), peps, ptr(py), ptr(pm), ptr(pr)
-    check(L.lib.mvlt_mlp_fwd(C.byref(a), stream_ptr()), "mvlt_mlp_fwd")
+    return a
+
+
+def mlp_fwd(x, w1, b1, w2, b2, residual, out, *dims, out_op=None, **kw):
+    """mlp_fwd(x, w1, b1, w2, b2, residual, out, M, Cdim, hid, *, row_scale, rows_per_scale, h_out, ln, out_op, post_ln)
+    ln = (gamma, beta, eps, y, mean, rstd): LayerNorm(residual) folded into the operand load -- `x` is then not read (may be None);
+    y (bf16 [M, C]) receives the normalised rows, mean / rstd (fp32 [M]) the row statistics.
+    out_op: optional bf16 [M, C] copy of the output; `out` (fp32) may be None when only the copy is wanted.
+    post_ln = (gamma, beta, eps, y, mean, rstd): LayerNorm of the OUTPUT rows (the next block's norm1) from the epilogue."""
+    check(L.lib.mvlt_mlp_fwd(C.byref(_mlp_fwd_args(x, w1, b1, w2, b2, residual, out, *dims, out_op=out_op, **kw)), stream_ptr()), "mvlt_mlp_fwd")
     return out if out is not None else out_op
 
 
-def mlp_bwd_dx(x, dy, w1, w1t, w2t, b1, out, M, Cdim, hid, *, row_scale=None, rows_per_scale=0, ln_bwd=None):
-    """ln_bwd = dict(x, mean, rstd, gamma, dx, dgamma, dbeta[, dx2, dx2_scale, dx2_rows_per_scale]): the backward of the LayerNorm in
-    front of the MLP from this kernel's epilogue -- dx (bf16 [M, C], may be `dy`) += LN backward in place, dx2 = its scaled copy,
-    dgamma / dbeta += the column sums (through per-workgroup partials and one mvlt_add_column_sums launch); `out` is not written."""
+def _mlp_bwd_dx_args(x, dy, w1, w1t, w2t, b1, out, M, Cdim, hid, *, row_scale=None, rows_per_scale=0, ln_bwd=None, lnb_partials=None):
+    """the mvlt_mlp_args of a mlp_bwd_dx / mlp_plan("bwd_dx", ...) call; lnb_partials: the per-workgroup column sums of ln_bwd (fp32 [ceil(M / 128), 2 C])"""
     assert x.dtype == dy.dtype == torch.bfloat16 and (out is None or out.dtype == torch.bfloat16)
     a = L.MlpArgs(x=ptr(x), dy=ptr(dy), w1=ptr(w1), wb=ptr(w1t), wc=ptr(w2t), b1=ptr(b1), row_scale=ptr(row_scale), rows_per_scale=rows_per_scale, M=M, C=Cdim, hid=hid)
     if ln_bwd is None:
         a.out = ptr(out)
-        check(L.lib.mvlt_mlp_bwd_dx(C.byref(a), stream_ptr()), "mvlt_mlp_bwd_dx")
-        return out
+        return a
     k = ln_bwd
     assert k["x"].dtype == torch.float32 and k["dx"].dtype == torch.bfloat16 and k["dx"].is_contiguous() and k["x"].is_contiguous()
     assert k["mean"].dtype == k["rstd"].dtype == k["gamma"].dtype == k["dgamma"].dtype == k["dbeta"].dtype == torch.float32
     dx2 = k.get("dx2")
     assert dx2 is None or (dx2.dtype == torch.bfloat16 and dx2.is_contiguous() and k["dx2_scale"].dtype == torch.float32)
-    nwg = (M + 127) // 128
-    partials = torch.empty(nwg, 2 * Cdim, device=x.device, dtype=torch.float32)
     a.lnb_x, a.lnb_mean, a.lnb_rstd, a.lnb_gamma, a.lnb_dx = ptr(k["x"]), ptr(k["mean"]), ptr(k["rstd"]), ptr(k["gamma"]), ptr(k["dx"])
-    a.lnb_dx2, a.lnb_dx2_scale, a.lnb_dx2_rows_per_scale, a.lnb_partials = ptr(dx2), ptr(k.get("dx2_scale")), int(k.get("dx2_rows_per_scale", 0)), ptr(partials)
+    a.lnb_dx2, a.lnb_dx2_scale, a.lnb_dx2_rows_per_scale, a.lnb_partials = ptr(dx2), ptr(k.get("dx2_scale")), int(k.get("dx2_rows_per_scale", 0)), ptr(lnb_partials)
+    return a
+
+
+def mlp_bwd_dx(x, dy, w1, w1t, w2t, b1, out, M, Cdim, hid, *, ln_bwd=None, **kw):
+    """mlp_bwd_dx(x, dy, w1, w1t, w2t, b1, out, M, Cdim, hid, *, row_scale, rows_per_scale, ln_bwd)
+    ln_bwd = dict(x, mean, rstd, gamma, dx, dgamma, dbeta[, dx2, dx2_scale, dx2_rows_per_scale]): the backward of the LayerNorm in
+    front of the MLP from this kernel's epilogue -- dx (bf16 [M, C], may be `dy`) += LN backward in place, dx2 = its scaled copy,
+    dgamma / dbeta += the column sums (through per-workgroup partials and one mvlt_add_column_sums launch); `out` is not written."""
+    if ln_bwd is None:
+        check(L.lib.mvlt_mlp_bwd_dx(C.byref(_mlp_bwd_dx_args(x, dy, w1, w1t, w2t, b1, out, M, Cdim, hid, **kw)), stream_ptr()), "mvlt_mlp_bwd_dx")
+        return out
+    partials = torch.empty((M + 127) // 128, 2 * Cdim, device=x.device, dtype=torch.float32)
+    a = _mlp_bwd_dx_args(x, dy, w1, w1t, w2t, b1, out, M, Cdim, hid, ln_bwd=ln_bwd, lnb_partials=partials, **kw)
     check(L.lib.mvlt_mlp_bwd_dx(C.byref(a), stream_ptr()), "mvlt_mlp_bwd_dx")
-    add_column_sums(partials, k["dgamma"], k["dbeta"])
-    return k["dx"]
+    add_column_sums(partials, ln_bwd["dgamma"], ln_bwd["dbeta"])
+    return ln_bwd["dx"]
 
 
 def add_column_sums(partials, dst0, dst1):
@@ -509,15 +523,38 @@ def add_column_sums(partials, dst0, dst1):
     check(L.lib.mvlt_add_column_sums(ptr(partials), rows, cols, cols, ptr(dst0), dst0.numel(), ptr(dst1), stream_ptr()), "mvlt_add_column_sums")
 
 
-def mlp_bwd_dw(x, dy, w1, w2t, b1, dw1, db1, dw2, db2, M, Cdim, hid, *, row_scale=None, rows_per_scale=0, partials=None, defer_fold=False):
-    """partials = the weight-gradient scratch of gemm_tn (FlatStore.tn_partials()): the token splits leave as bf16 partial tiles + the ordered fold instead of fp32 atomics;
-    defer_fold: folded with the other pending ones (tn_fold_flush before anything reads dw1 / dw2)"""
+def _mlp_bwd_dw_args(x, dy, w1, w2t, b1, dw1, db1, dw2, db2, M, Cdim, hid, *, row_scale=None, rows_per_scale=0, partials=None, defer_fold=False):
+    """the mvlt_mlp_args of a mlp_bwd_dw / mlp_plan("bwd_dw", ...) call"""
     assert x.dtype == dy.dtype == torch.bfloat16 and dw1.dtype == torch.float32
     a = L.MlpArgs(x=ptr(x), dy=ptr(dy), w1=ptr(w1), wc=ptr(w2t), b1=ptr(b1), row_scale=ptr(row_scale), rows_per_scale=rows_per_scale,
                   dw1=ptr(dw1), db1=ptr(db1), dw2=ptr(dw2), db2=ptr(db2), M=M, C=Cdim, hid=hid)
     if partials is not None:
         a.partials, a.partials_bytes, a.defer_fold = ptr(partials), partials.numel() * partials.element_size(), 1 if defer_fold else 0
-    check(L.lib.mvlt_mlp_bwd_dw(C.byref(a), stream_ptr()), "mvlt_mlp_bwd_dw")
+    return a
+
+
+def mlp_bwd_dw(*args, **kw):
+    """mlp_bwd_dw(x, dy, w1, w2t, b1, dw1, db1, dw2, db2, M, Cdim, hid, *, row_scale, rows_per_scale, partials, defer_fold)
+    partials = the weight-gradient scratch of gemm_tn (FlatStore.tn_partials()): the token splits leave as bf16 partial tiles + the ordered fold instead of fp32 atomics;
+    defer_fold: folded with the other pending ones (tn_fold_flush before anything reads dw1 / dw2)"""
+    check(L.lib.mvlt_mlp_bwd_dw(C.byref(_mlp_bwd_dw_args(*args, **kw)), stream_ptr()), "mvlt_mlp_bwd_dw")
+
+
+_MLP_PLANS = {"fwd": (_mlp_fwd_args, "mvlt_mlp_fwd_plan"), "bwd_dx": (_mlp_bwd_dx_args, "mvlt_mlp_bwd_dx_plan"), "bwd_dw": (_mlp_bwd_dw_args, "mvlt_mlp_bwd_dw_plan")}
+
+
+def mlp_plan(which, *args, **kw):
+    """what mlp_fwd / mlp_bwd_dx / mlp_bwd_dw (which = "fwd" / "bwd_dx" / "bwd_dw") would launch for the same arguments (mvlt_mlp_plan of include/mvlt_hip_plan.h,
+    .name as _lib.last_kernel() prints it); nothing is launched and no device is touched.  A single _lib.MlpArgs stands for the arguments as well (the plan looks at
+    pointers, it never follows them).  With ln_bwd the per-workgroup partials mlp_bwd_dx allocates are stood in for by ln_bwd["dx"]."""
+    make, entry = _MLP_PLANS[which]
+    if len(args) == 1 and isinstance(args[0], L.MlpArgs):
+        a = args[0]
+    else:
+        if which == "bwd_dx" and kw.get("ln_bwd") is not None:
+            kw.setdefault("lnb_partials", kw["ln_bwd"]["dx"])
+        a = make(*args, **kw)
+    return Plan(getattr(L.lib, entry), a, L.MlpPlan, L.lib.mvlt_mlp_plan_name)
 
 
 # ------------------------------------------------------------------ device-side batch preparation (csrc/batchprep.hip)

@@ -2,9 +2,9 @@
 (tests/test_fusedln_edges_gpu.py; the premises are pinned on the CPU by tests/test_fusedln_cases_cpu.py; the argument is in
 docs/fused_layernorm_edges.md).  The four sites:
   1  csrc/gemm_common.h  nt_epilogue_lean<.., EPIX = 8>   post_y / post_mean / post_rstd = LN(C row), the row split over two waves
-  2  csrc/mlp.hip        mlp_epilogue<C, 0>, p.post_y      LN of the output row (the next block's norm1)
-  3  csrc/mlp.hip        mlp_epilogue<C, 1>, p.lnb_x       norm2 backward: dx += .. in place, dx2, dgamma / dbeta through per-workgroup partials
-  4  csrc/mlp.hip        mlp_load_rows<C, 0>, p.ln_x       norm2 folded into the operand load
+  2  csrc/mlp_common.h   mlp_epilogue<C, 0>, p.post_y      LN of the output row (the next block's norm1)
+  3  csrc/mlp_common.h   mlp_epilogue<C, 1>, p.lnb_x       norm2 backward: dx += .. in place, dx2, dgamma / dbeta through per-workgroup partials
+  4  csrc/mlp_common.h   mlp_load_rows<C, 0>, p.ln_x       norm2 folded into the operand load
 
 Plain torch on the CPU, no GPU and no library.  Builders, references, bars and TOL are those of tests/rowwise_cases.py, the saturated integer MLP data
 that of tests/mlp_cases.py.  What is new here is how a row a fused site normalises becomes KNOWN EXACTLY:
@@ -40,6 +40,11 @@ DX2_SCALES = (0.0, 1.0 / 0.8, 2.0)
 DX2_RPS = 37                                   # != rows_per_scale (33, 50): the two factor tables are indexed apart
 FOLD_HID = ((64, "mlp_fused_kernel"), (128, "mlp_pipe_kernel"))
 FOLD_M = (1, 33, 129)
+# the family literals above against the dispatch itself (csrc/mlp_plan.h), where the library is loadable: no launch of these sites asks for a pre-activation
+for _C in MLP_C:
+    for _hid, _fam in POST_HID + FOLD_HID:
+        _fwd, _dx = mc.planned("fwd", _C, _hid, 129), mc.planned("bwd_dx", _C, _hid, 129)
+        assert _fwd is None or (_fwd.name, _dx.name) == (f"{_fam}<{_C}, 0>", f"{_fam}<{_C}, 1>"), (_C, _hid, _fam)
 
 
 def ints(shape, lo, hi, seed):

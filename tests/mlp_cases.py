@@ -1,5 +1,6 @@
 """Test infrastructure: operands, float64 references and bounds of the exact fused-MLP tests (tests/test_mlp_exact_gpu.py; the premises are pinned on
-the CPU by tests/test_mlp_cases_cpu.py).  The kernels: csrc/mlp.hip (mlp_fused_kernel, mlp_pipe_kernel, mlp_wgrad_kernel, mlp_wgrad2_kernel), the GELU
+the CPU by tests/test_mlp_cases_cpu.py).  The kernels: csrc/mlp_fused.hip (mlp_fused_kernel), csrc/mlp_pipe.hip (mlp_pipe_kernel), csrc/mlp_wgrad.hip
+(mlp_wgrad_kernel, mlp_wgrad2_kernel) -- which of them a launch gets is decided in csrc/mlp_plan.h --, the GELU
 epilogues of the NT GEMMs (csrc/gemm_common.h: nt_epilogue_lean) and gelu_bwd.  Plain torch on the CPU, no GPU and no library.  The argument is written down in docs/mlp_exact.md.
 
 Every pre-activation is SATURATED: an integer h with |h| >= SAT.  For a unit that is on (h >= SAT) every GELU form of the tree gives Phi and GELU' within
@@ -51,9 +52,22 @@ def off_units(hid):
     return (j + j // 32) % 2 == 0
 
 
+def planned(which, C, hid, M, *, h_out=False, rps=0):
+    """what ops.mlp_plan names for a launch of this shape ("fwd" / "bwd_dx" / "bwd_dw"; rps: rows_per_scale of a row_scale, 0 for none): the struct of
+    include/mvlt_hip_plan.h, .name the kernel.  None where the library is not loadable (these modules otherwise need neither it nor a GPU).  The pointers
+    are placeholders: the plan never follows one."""
+    try:
+        from mvlt_amd import _lib as L, ops
+    except (ImportError, OSError):
+        return None
+    a = L.MlpArgs(x=0x100, dy=0x200, w1=0x300, wb=0x400, wc=0x500, b1=0x600, b2=0x700, residual=0x800, out=0x900, h_out=0xa00 if h_out else None,
+                  dw1=0xb00, db1=0xc00, dw2=0xd00, db2=0xe00, row_scale=0xf00 if rps else None, rows_per_scale=rps, M=M, C=C, hid=hid)
+    return ops.mlp_plan(which, a)
+
+
 def wgrad_split(C, hid, M):
-    """the token splits of a weight-gradient launch.  This RESTATES the split arithmetic of launch_wgrad (csrc/mlp.hip) and exists only to prove that a
-    case reaches the loop it is meant to reach: 64-token tiles per split, splits, rows per split."""
+    """the token splits of a weight-gradient launch.  This RESTATES the split arithmetic of choose_dw (csrc/mlp_plan.h) and exists only to prove that a
+    case reaches the loop it is meant to reach: 64-token tiles per split, splits, rows per split.  Where the library is loadable the plan must say the same."""
     ny = hid // 128
     splits = ((512 if C == 64 else 256) + ny - 1) // ny
     splits = (splits + 7) // 8 * 8
@@ -61,6 +75,8 @@ def wgrad_split(C, hid, M):
     splits = max(1, min(splits, mtiles))
     m_per_split = (mtiles + splits - 1) // splits * 64
     splits = (M + m_per_split - 1) // m_per_split
+    p = planned("bwd_dw", C, hid, M)
+    assert p is None or (p.m_per_split, p.splits, p.ny, p.grid) == (m_per_split, splits, ny, 8 * ((splits + 7) // 8) * ny)
     return NS(tiles=m_per_split // 64, splits=splits, m_per_split=m_per_split, idle=8 * ((splits + 7) // 8) - splits)
 
 

@@ -1,9 +1,9 @@
 """GPU: the LayerNorm arithmetic that is written out by hand inside OTHER kernels, against the float64 references of tests/rowwise_cases.py on rows that
 are known exactly (tests/fusedln_cases.py; premises and the eight wrong formulas: tests/test_fusedln_cases_cpu.py; argument: docs/fused_layernorm_edges.md):
   site 1  csrc/gemm_common.h  nt_epilogue_lean<.., EPIX = 8>   post_y / post_mean / post_rstd = LN(C row), the row split over two waves (LDS exchange)
-  site 2  csrc/mlp.hip        mlp_epilogue<C, 0>, p.post_y      LN of the output row, xor-shuffles over C / 8 lanes
-  site 3  csrc/mlp.hip        mlp_epilogue<C, 1>, p.lnb_x       norm2 backward: dx += .. in place, dx2, dgamma / dbeta through per-workgroup partials
-  site 4  csrc/mlp.hip        mlp_load_rows<C, 0>, p.ln_x       norm2 folded into the operand load
+  site 2  csrc/mlp_common.h   mlp_epilogue<C, 0>, p.post_y      LN of the output row, xor-shuffles over C / 8 lanes
+  site 3  csrc/mlp_common.h   mlp_epilogue<C, 1>, p.lnb_x       norm2 backward: dx += .. in place, dx2, dgamma / dbeta through per-workgroup partials
+  site 4  csrc/mlp_common.h   mlp_load_rows<C, 0>, p.ln_x       norm2 folded into the operand load
 
 Bars: only rowwise_cases.TOL (1e-3 fp32, 2e-2 bf16), per row or per column, never against a global maximum:
   y (bf16 at every site)   per element, TOL[bf16] x max|ref| over the row

@@ -350,7 +350,7 @@ def test_plan_header_and_binding_agree():
     import mvlt_amd._lib as L
     hdr = open(os.path.join(ROOT, "include", "mvlt_hip_plan.h")).read()
     protos, structs = _header_abi(re.sub(r"(\w+)\[(\d+)\]", r"\1__\2", hdr))
-    assert set(protos) == set(L.PLAN_PROTOTYPES) and set(structs) == {n for n, _ in L.PLAN_STRUCTS} == {"mvlt_gemm_plan", "mvlt_attn_plan"}
+    assert set(protos) == set(L.PLAN_PROTOTYPES) and set(structs) == {n for n, _ in L.PLAN_STRUCTS} == {"mvlt_gemm_plan", "mvlt_attn_plan", "mvlt_mlp_plan"}
     assert not set(L.PLAN_PROTOTYPES) & (set(L.PROTOTYPES) | set(L.EXT_PROTOTYPES) | set(L.EMA_PROTOTYPES))
     classes = dict(L.STRUCTS + L.PLAN_STRUCTS)
     scalars = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "char*": C.c_char_p}
@@ -368,8 +368,8 @@ def test_plan_header_and_binding_agree():
         for (f, ctype), (written_f, written_t) in zip(cls._fields_, fields):
             base, _, n = written_f.partition("__")
             assert f == base and ctype is ({"int": C.c_int, "long": C.c_long}[written_t] * int(n) if n else {"int": C.c_int, "long": C.c_long}[written_t]), (f, written_f)
-    assert L.lib.mvlt_plan_version() == L.PLAN_VERSION == int(re.search(r"#define MVLT_PLAN_VERSION (\d+)", hdr).group(1)) == 2
-    assert L.lib.mvlt_gemm_plan_sizeof() == C.sizeof(L.GemmPlan) and L.lib.mvlt_attn_plan_sizeof() == C.sizeof(L.AttnPlan)
+    assert L.lib.mvlt_plan_version() == L.PLAN_VERSION == int(re.search(r"#define MVLT_PLAN_VERSION (\d+)", hdr).group(1)) == 3
+    assert L.lib.mvlt_gemm_plan_sizeof() == C.sizeof(L.GemmPlan) and L.lib.mvlt_attn_plan_sizeof() == C.sizeof(L.AttnPlan) and L.lib.mvlt_mlp_plan_sizeof() == C.sizeof(L.MlpPlan)
     afams = dict(re.findall(r"#define (MVLT_ATTN_\w+) (\d+)", hdr))
     assert len(afams) == 6 and sorted(map(int, afams.values())) == list(range(1, 7))
     fams = dict(re.findall(r"#define (MVLT_GEMM_\w+) (\d+)", hdr))

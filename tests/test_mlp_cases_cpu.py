@@ -50,7 +50,9 @@ def test_forward_and_dx_case(C, hid, h_out, fam, M, rps, factors, off):
     c = mc.fwd_case(C, hid, M, rps, factors, off)
     common(c, ("out", "dx"))
     assert mc.bf16_exact(c.ref.dx) and float(c.ref.dx.abs().max()) <= 256, "dx is rounded by its bf16 store"
-    assert (fam == "mlp_pipe_kernel") == (not h_out and hid >= 128)        # launch<C, MODE>'s rule, restated
+    assert (fam == "mlp_pipe_kernel") == (not h_out and hid >= 128)        # the rule of choose() in csrc/mlp_plan.h, restated
+    fwd, dx = mc.planned("fwd", C, hid, M, h_out=h_out, rps=rps), mc.planned("bwd_dx", C, hid, M, rps=rps)
+    assert fwd is None or (fwd.name, dx.name) == (f"{fam}<{C}, 0>", f"{'mlp_fused_kernel' if hid < 128 else 'mlp_pipe_kernel'}<{C}, 1>")
 
 
 def check_partials(c):
@@ -67,6 +69,8 @@ def test_weight_gradient_case(name, C, hid, M, scaled):
     check_partials(c)
     sp = mc.wgrad_split(C, hid, M)
     assert (c.rps % 64 == 0), "the tile-uniform kernel"
+    p = mc.planned("bwd_dw", C, hid, M, rps=c.rps)
+    assert p is None or (p.name, p.m_per_split, p.splits) == (f"mlp_wgrad2_kernel<{C}, {4 if C == 64 else 8}>", sp.m_per_split, sp.splits)
     if name.startswith("single"):
         assert sp.tiles == 1
         return
@@ -95,6 +99,8 @@ def test_per_row_factor_case(C, hid, rps, factors):
     c = mc.r2_case(C, hid, rps, factors)
     common(c, ("dw1", "db1", "dw2"))
     assert rps % 64 != 0 and c.scale is not None, "the per-row kernel"
+    p = mc.planned("bwd_dw", C, hid, c.M, rps=rps)
+    assert p is None or p.name == f"mlp_wgrad_kernel<{C}>"
     samples = [len(set(range(t, min(t + 64, c.M))[i] // rps for i in range(min(64, c.M - t)))) for t in range(0, c.M, 64)]
     if rps == 100:
         assert max(samples) == 2

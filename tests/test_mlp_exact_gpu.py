@@ -1,15 +1,16 @@
-"""GPU: the fused-MLP kernels of csrc/mlp.hip, the GELU epilogues of the GEMMs and gelu_bwd on SATURATED integer data (tests/mlp_cases.py, whose premises
+"""GPU: the fused-MLP kernels of csrc/mlp_fused.hip, mlp_pipe.hip and mlp_wgrad.hip, the GELU epilogues of the GEMMs and gelu_bwd on SATURATED integer data (tests/mlp_cases.py, whose premises
 tests/test_mlp_cases_cpu.py pins; the argument is in docs/mlp_exact.md).  Every pre-activation is an integer with |h| >= 16: a unit that is on passes h and
 dG through its bf16 tile unchanged, a unit that is off contributes at most a derived, per-element bound, and the MLP becomes two integer GEMMs whose float64
 reference must be met bit for bit -- one dropped row, one misplaced hidden unit or one row under another sample's DropPath factor is a hard mismatch with a
-row and a column to print.  Every case asserts the kernel family it meant to reach.  Operands are row slices of buffers whose other rows hold a finite poison
+row and a column to print.  Every case asserts the kernel family it meant to reach, and that the launch ran what ops.mlp_plan names
+for the same arguments.  Operands are row slices of buffers whose other rows hold a finite poison
 (7.0: a wrong read shows as an integer error; NaN would not pass the zero page the kernels substitute past the last row), outputs are slices of
 sentinel-filled buffers whose surroundings must come back unchanged."""
 import pytest
 import torch
 
 from tests import mlp_cases as mc
-from tests.test_exact_gpu import dev, ops, ran                       # noqa: F401  (ops is the module-scoped fixture)
+from tests.test_exact_gpu import dev, last_kernel, ops, ran          # noqa: F401  (ops is the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -52,6 +53,7 @@ def test_mlp_forward_and_dx(ops, C, hid, h_out, fam, M, rps, factors, off):
     hbuf, hst = guarded(shape=(M, hid), dtype=BF) if h_out else (None, None)
     ops.mlp_fwd(d.x, d.w1, d.b1, d.w2, d.b2, d.res, out, M, C, hid, h_out=hst, **d.kw)
     ran(f"{fam}<{C}, 0>")
+    assert ops.mlp_plan("fwd", d.x, d.w1, d.b1, d.w2, d.b2, d.res, out, M, C, hid, h_out=hst, **d.kw).name == last_kernel()
     mc.compare(out, d.ref.out, d.bound.out, what + " out")
     untouched(obuf, "out")
     if h_out:
@@ -63,6 +65,7 @@ def test_mlp_forward_and_dx(ops, C, hid, h_out, fam, M, rps, factors, off):
         pbuf, op = guarded(shape=(M, C), dtype=BF)
         ops.mlp_fwd(d.x, d.w1, d.b1, d.w2, d.b2, d.res, o2 if with_out else None, M, C, hid, out_op=op, h_out=hst, **d.kw)
         ran(f"{fam}<{C}, 0>")
+        assert ops.mlp_plan("fwd", d.x, d.w1, d.b1, d.w2, d.b2, d.res, o2 if with_out else None, M, C, hid, out_op=op, h_out=hst, **d.kw).name == last_kernel()
         assert torch.equal(op, out.to(BF)), "out_op is not out rounded once"
         mc.compare(op, d.ref.out, d.bound.out, what + " out_op")
         assert torch.equal(o2, out) if with_out else bool((o2buf == POISON).all())
@@ -70,6 +73,7 @@ def test_mlp_forward_and_dx(ops, C, hid, h_out, fam, M, rps, factors, off):
     xbuf, dx = guarded(shape=(M, C), dtype=BF)
     ops.mlp_bwd_dx(d.x, d.dy, d.w1, d.w1t, d.w2t, d.b1, dx, M, C, hid, **d.kw)
     ran(f"{'mlp_fused_kernel' if hid < 128 else 'mlp_pipe_kernel'}<{C}, 1>")        # no pre-activation output on this side: the pipelined kernel from 128 units on
+    assert ops.mlp_plan("bwd_dx", d.x, d.dy, d.w1, d.w1t, d.w2t, d.b1, dx, M, C, hid, **d.kw).name == last_kernel()
     mc.compare(dx, d.ref.dx, d.bound.dx, what + " dx")
     untouched(xbuf, "dx")
 
@@ -85,6 +89,8 @@ def run_dw(ops, c, d, **kw):
     for t in (g.dw1, g.dw2, g.db1, g.db2):
         t.fill_(3.0)
     ops.mlp_bwd_dw(d.x, d.dy, d.w1, d.w2t, d.b1, g.dw1, g.db1, g.dw2, g.db2, c.M, c.C, c.hid, **d.kw, **kw)
+    g.launched = last_kernel()
+    g.plan = ops.mlp_plan("bwd_dw", d.x, d.dy, d.w1, d.w2t, d.b1, g.dw1, g.db1, g.dw2, g.db2, c.M, c.C, c.hid, **d.kw, **kw)
     return g
 
 
@@ -106,14 +112,17 @@ def test_mlp_weight_gradients_tile_uniform(ops, name, C, hid, M, scaled):
     fam = f"mlp_wgrad2_kernel<{C}, {4 if C == 64 else 8}>"
     g = run_dw(ops, c, d)
     ran(fam)
+    assert g.plan.name == g.launched and g.plan.fold == 0
     check_dw(g, d, name + " atomic")
     scratch = torch.full((16 * 1024 * 1024,), POISON, device=dev(), dtype=BF)
     now = run_dw(ops, c, d, partials=scratch)
     ran("tn_fold_kernel")
+    assert now.plan.name == fam and now.plan.fold == 1 and now.plan.partials_need <= scratch.numel() * 2       # (the launch ran the two folds behind the planned kernel)
     check_dw(now, d, name + " immediate fold")
     scratch.fill_(POISON)
     later = run_dw(ops, c, d, partials=scratch, defer_fold=True)
     ran(fam)
+    assert later.plan.name == later.launched and later.plan.fold == 1
     assert bool((later.dw1 == 3.0).all()) and bool((later.dw2 == 3.0).all()), "a deferring launch touched dW before the flush"
     ops.tn_fold_flush(scratch)
     ran("tn_fold_multi_kernel")
@@ -130,6 +139,7 @@ def test_mlp_weight_gradients_factor_per_row(ops, C, hid, rps, factors):
     d = on_device(c)
     g = run_dw(ops, c, d)
     ran(f"mlp_wgrad_kernel<{C}>")
+    assert g.plan.name == g.launched and g.plan.fold == 0
     check_dw(g, d, f"rows_per_scale {rps}")
 
 

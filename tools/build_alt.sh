@@ -11,7 +11,7 @@ objs=$(ls mvlt_amd/csrc/_obj/*.o)
 alt=""
 for src in ${srcs//,/ }; do
   extra=""
-  [ "$src" = "mlp.hip" ] && extra="-fno-slp-vectorize"
+  case "$src" in mlp_fused.hip|mlp_pipe.hip|mlp_wgrad.hip) extra="-fno-slp-vectorize";; esac      # as mvlt_amd/build.py EXTRA
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -w $extra "$@" -c mvlt_amd/csrc/$src -o ab/${name}_${src%.hip}.o &
   objs=$(echo "$objs" | grep -v "/${src%.hip}.o")
   alt="$alt ab/${name}_${src%.hip}.o"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction mix of the hottest loop of every kernel in a HIP source (hipcc -S, no GPU needed):
-    python tools/isa_mix.py mvlt_amd/csrc/mlp.hip [name filter]
+    python tools/isa_mix.py mvlt_amd/csrc/mlp_pipe.hip [name filter]
 Per kernel: VGPR / AGPR / LDS / occupancy from the metadata, and for the largest loop (label .. backward branch) the number of
 MFMA, transcendental (quarter rate), packed, accvgpr-move, other VALU, LDS, VMEM, SALU and s_waitcnt instructions.  The VALU
 issue estimate counts 4 cycles per VALU instruction and 16 per transcendental and per 16x16x32 bf16 MFMA."""
@@ -13,7 +13,7 @@ from collections import Counter
 def main():
     src, flt = sys.argv[1], (sys.argv[2] if len(sys.argv) > 2 else "")
     import os
-    extra = os.environ.get("MVLT_ISA_FLAGS", "").split() + (["-fno-slp-vectorize"] if src.endswith("mlp.hip") else [])    # the build's own flags
+    extra = os.environ.get("MVLT_ISA_FLAGS", "").split() + (["-fno-slp-vectorize"] if os.path.basename(src) in ("mlp_fused.hip", "mlp_pipe.hip", "mlp_wgrad.hip") else [])    # the build's own flags
     asm = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", *extra, "-S", "--cuda-device-only", src, "-o", "-"],
                          capture_output=True, text=True).stdout
     lines = asm.split("\n")

@@ -1,6 +1,6 @@
 #!/bin/bash
 # the model-level parity tests under other arithmetic orderings -- the default build, and alternative libraries where they were built: the sigmoid-form GELU
-# instead of the polynomials (bash tools/build_alt.sh sigm gemm_nt_dma.hip,gemm_nt_p8.hip,mlp.hip -DMVLT_GELU_POLY=0 -- the GEMM files whose epilogues
+# instead of the polynomials (bash tools/build_alt.sh sigm gemm_nt_dma.hip,gemm_nt_p8.hip,mlp_fused.hip,mlp_pipe.hip,mlp_wgrad.hip -DMVLT_GELU_POLY=0 -- the GEMM files whose epilogues
 # carry GELU / GELU'): the tightest margins of each run.
 #   bash tools/parity_orderings.sh > rNN_parity_orderings.txt
 cd "${GRAFT_REPO_ROOT:-.}"
