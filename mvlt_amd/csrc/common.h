@@ -161,7 +161,8 @@ __device__ __forceinline__ void gelu_erf_both2(f32x2 x, f32x2& g, f32x2& dg) {
 // weight-gradient kernels).  Phi(x) - 1/2 and GELU'(x) - 1/2 are odd: x * P(x^2) on |x| <= 4, clamped beyond (Phi(4) = 1 - 3.2e-5,
 // GELU'(4) = 1 + 5.0e-4), near-minimax fits (the fitting recipe is in DESIGN 6.0).  v_exp_f32 / v_rcp_f32 cost 2.3 plain VALU
 // instructions each on gfx950 (profiles/r03_valu_rates.txt): GELU' is 10 plain instructions here against 15 + 2 transcendentals
-// (19.6 units) above.  |GELU' error| <= 2.8e-4 + the 5e-4 tail, |Phi error| <= 1.0e-4 absolute (fp32 Horner).
+// (19.6 units) above.  |GELU' error| <= 2.8e-4 + the 5e-4 tail, |Phi error| <= 1.05e-4 absolute (fp32 Horner; the largest over every bf16
+// input is 1.040e-4 at |x| = 2.594: tests/test_gelu_cases_cpu.py asserts the bound and the place).
 // In the bf16 GEMM epilogues (EPI 3 / 4, gemm_common.h) round 3 measured no gain on the 128-wide kernels (four workgroups per CU hide the epilogue's VALU work); on the
 // 8-wave kernels (two waves per SIMD, VALU-bound epilogue) GELU' is 10 instructions instead of 19.6 issue units: stage-4 GELU' dgrad 179 -> 157 us, stage-3 204 -> 181 us
 // (same-box A/B, round 4).  One default for the GEMM and the fused-MLP kernels; tools/parity_orderings.sh builds the other arithmetic ordering with it.
@@ -191,7 +192,9 @@ __device__ __forceinline__ float gelu_poly_dg_s(float xc, float s) {           /
 }
 // The Phi polynomial overshoots past its fit range (Phi_poly(4) = 1 + 7.2e-5, Phi_poly(-4) = -7.2e-5): clamped at +-4 the forward returned
 // +7.2e-5 |x| for x < -4 -- wrong sign, growing with |x|.  It crosses 1 / 0 at |x| = 3.98504; clamped at 3.985 it saturates at
-// 1 - 6e-7 / 6e-7 (true Phi(3.985) = 1 - 3.4e-5: inside the fit's 1e-4 bound), so the tail is x * 6e-7 with the right sign, no extra instruction.
+// 1 - 6e-7 / 6e-7 in exact arithmetic (true Phi(3.985) = 1 - 3.4e-5: inside the fit's 1e-4 bound), no extra instruction.  The fp32 Horner below (terms of
+// magnitude 3.5 cancel) lands at 1 + 3.6e-7 / -3.6e-7 instead: the tail is |x| * 3.6e-7, 200 times smaller than at 4, but its sign is not the right one
+// (tests/test_gelu_cases_cpu.py asserts |tail| <= 4e-7 |x|; docs/gelu_range.md).
 #define MVLT_GELU_PHI_CLAMP 3.985f
 __device__ __forceinline__ float gelu_poly1(float x) {
   const float xc = __builtin_amdgcn_fmed3f(x, -MVLT_GELU_PHI_CLAMP, MVLT_GELU_PHI_CLAMP);
