@@ -1,4 +1,4 @@
-"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h, include/mvlt_hip_ema.h and include/mvlt_hip_plan.h).
+"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h, include/mvlt_hip_ema.h, include/mvlt_hip_plan.h and include/mvlt_hip_opt.h).
 
 The product path has NO fallback: importing this module without the built library, or calling an op without a
 GPU, raises.  torch is used only for device memory and streams.
@@ -272,6 +272,22 @@ _plan_sizes = [(n, getattr(lib, n + "_sizeof")(), C.sizeof(c)) for n, c in PLAN_
 if lib.mvlt_plan_version() != PLAN_VERSION or any(have != want for _, have, want in _plan_sizes):
     raise ImportError(f"plan entry points mismatch: {LIB_PATH} is version {lib.mvlt_plan_version()}, the binding is version {PLAN_VERSION}; (struct, bytes in the library, "
                       f"bytes in the binding): {_plan_sizes} (stale build? run python -m mvlt_amd.build)")
+
+# The entry points of include/mvlt_hip_opt.h (AdamW with a learning rate and a weight decay per parameter group, docs/param_groups.md): a table of their own,
+# bound and version-checked like the EMA one (tests/test_param_groups_cpu.py compares it with that header).
+OPT_PROTOTYPES = {
+    "mvlt_opt_version": (_i, []),
+    "mvlt_adamw_step_groups": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _vp, _vp, _vp]),      # table: a DEVICE array of float[n_groups][2]
+}
+for _name, (_res, _args) in OPT_PROTOTYPES.items():
+    if not hasattr(lib, _name):
+        raise ImportError(f"{LIB_PATH} does not export {_name} (include/mvlt_hip_opt.h): stale build? run python -m mvlt_amd.build")
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
+OPT_VERSION = 1          # include/mvlt_hip_opt.h MVLT_OPT_VERSION this binding was written against
+if lib.mvlt_opt_version() != OPT_VERSION:
+    raise ImportError(f"optimizer entry points mismatch: {LIB_PATH} is version {lib.mvlt_opt_version()}, the binding is version {OPT_VERSION} (stale build? run python -m mvlt_amd.build)")
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 

@@ -332,6 +332,25 @@ def adamw_step_gated(p, g, m, v, p16, n, hp, decay_mask, gate):
     check(L.lib.mvlt_adamw_step_gated(ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), n, ptr(hp), ptr(decay_mask), ptr(gate), stream_ptr()), "mvlt_adamw_step_gated")
 
 
+OPT_FROZEN = 255          # group byte of an element no launch steps (MVLT_OPT_FROZEN in include/mvlt_hip_opt.h): a frozen parameter or an alignment gap
+OPT_MAX_GROUPS = 254      # MVLT_OPT_MAX_GROUPS
+
+
+def adamw_step_groups(p, g, m, v, p16, n, hp, group_of, table, n_groups, *, gscale_dev=None, gate=None):
+    """`adamw_step` with a learning rate and a weight decay per parameter group (include/mvlt_hip_opt.h).  hp: the fp32[8] row of `adamw_step`, its slots 0
+    (lr) and 4 (weight_decay) ignored; table: fp32 [n_groups, 2] = {lr, weight_decay} on the device; group_of: one uint8 per element -- the element's group, or
+    OPT_FROZEN (as any byte >= n_groups): p / m / v / p16 are left alone.  gscale_dev as for `adamw_step`, gate as for `adamw_step_gated`; at most one."""
+    for t in (p, g, m, v, hp, table):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert min(p.numel(), g.numel(), m.numel(), v.numel(), group_of.numel()) >= n and hp.numel() >= 8 and table.numel() >= 2 * n_groups
+    assert p16 is None or (p16.dtype == torch.bfloat16 and p16.is_contiguous() and p16.numel() >= n)
+    assert group_of.dtype == torch.uint8 and group_of.is_contiguous()
+    assert gscale_dev is None or gscale_dev.dtype == torch.float32
+    assert gate is None or (gate.dtype == torch.float32 and gate.numel() >= 4 and gate.is_contiguous())
+    check(L.lib.mvlt_adamw_step_groups(ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), n, ptr(hp), ptr(group_of), ptr(table), n_groups, ptr(gscale_dev), ptr(gate),
+                                       stream_ptr()), "mvlt_adamw_step_groups")
+
+
 def ema_update(ema, p, ema16, n, decay, one_minus_decay, mask=None):
     """ema[0:n] = ema * decay + p * one_minus_decay, the two products and the sum each rounded to fp32 on its own (timm's ModelEma formula in torch's
     bits); ema16 (bf16, optional) receives the bf16 of the new values in the same pass; mask (uint8, optional): elements whose byte is ADAMW_FROZEN are

@@ -7,6 +7,10 @@ get weight_decay 0, everything else args.weight_decay.  It is a torch.optim.Opti
 lr schedulers (`param_groups[i]['lr']`) and state_dict()/load_state_dict() keep working; `param_groups[0]` is the
 no-decay group and `[1]` the decay group, like timm's add_weight_decay.
 
+param_groups=[...] (docs/param_groups.md): the caller's own groups, each with its `lr` and `weight_decay` -- a head that trains faster than the backbone, or
+layer-wise lr decay (`layer_decay_groups` below).  While every group has the same lr and at most one non-zero weight decay the step is the launch above;
+otherwise it is one launch of mvlt_adamw_step_groups (include/mvlt_hip_opt.h), which looks both up per element.  betas and eps are one for all groups.
+
 Frozen parameters (requires_grad=False) are left alone, as torch.optim.AdamW leaves a parameter without `.grad` alone: the groups hold every
 parameter of the model, and the per-element mask of the kernel carries a third value for the elements of frozen ones (neither they nor their
 moments nor their bf16 copies are written).  The mask follows requires_grad from step to step, so un-freezing needs no new optimizer.
@@ -15,6 +19,8 @@ skip_nonfinite=True (docs/nonfinite_guard.md): with engine.BF16Scaler(skip_nonfi
 -- the decision is taken on the device (FlatStore.gate_grads) and obeyed by the kernel, the host never reads it.  One difference from GradScaler follows:
 `_step`, the host count behind the bias corrections, counts ATTEMPTED steps, so after a skip the corrections are those of t + 1.
 """
+import re
+
 import torch
 
 from . import ops
@@ -73,24 +79,55 @@ def clip_grad_norm_(model, max_norm):
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, skip_nonfinite=False):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, skip_nonfinite=False, param_groups=None):
         model = _unwrap(model)
         self.model = model
         self.skip_nonfinite = bool(skip_nonfinite)
         self._pending_counts = None           # (applied, skipped) of a checkpoint loaded before the flat store exists
-        no_decay, decay = [], []
         # every parameter of the model is in a group, frozen ones too: `requires_grad` decides per step (the mask byte of mvlt_adamw_step), so a
         # parameter frozen now and un-frozen later starts stepping without a new optimizer
-        for name, p in model.named_parameters():
-            (no_decay if (p.dim() == 1 or name.endswith(".bias")) else decay).append(p)
-        groups = [dict(params=no_decay, weight_decay=0.0), dict(params=decay, weight_decay=weight_decay)]
+        if param_groups is None:
+            no_decay, decay = [], []
+            for name, p in model.named_parameters():
+                (no_decay if (p.dim() == 1 or name.endswith(".bias")) else decay).append(p)
+            groups = [dict(params=no_decay, weight_decay=0.0), dict(params=decay, weight_decay=weight_decay)]
+        else:
+            groups = self._checked_groups(model, param_groups, tuple(betas), eps)
         super().__init__(groups, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._step = 0
-        self._m = self._v = self._wd_mask = self._mask_key = None
+        self._m = self._v = self._wd_mask = self._group_of = self._mask_key = None
         self._frozen_ranges = []              # maximal [lo, hi) runs of the flat buffer whose every element is frozen (gaps inside a run included)
         self._hp = self._hp_pin = None
         self._hp_ev = [None] * 4
         self._pending = None                  # (m, v) of a checkpoint loaded before the flat store exists
+
+    @staticmethod
+    def _checked_groups(model, param_groups, betas, eps):
+        """the caller's groups as torch.optim.Optimizer takes them (`params` a list; every other key -- lr, weight_decay, name, lr_scale, ... -- as it
+        came), or a ValueError that names the offender"""
+        groups = [dict(g, params=list(g["params"])) if isinstance(g, dict) and "params" in g else g for g in param_groups]
+        if not groups or not all(isinstance(g, dict) and "params" in g for g in groups):
+            raise ValueError("FusedAdamW: param_groups must be a non-empty list of dicts with a 'params' entry")
+        if len(groups) > ops.OPT_MAX_GROUPS:
+            raise ValueError(f"FusedAdamW: {len(groups)} parameter groups, the kernel's group byte takes {ops.OPT_MAX_GROUPS} at the most")
+        label = lambda i: f"group {i}" + (f" ({groups[i]['name']!r})" if "name" in groups[i] else "")
+        names = {id(p): n for n, p in model.named_parameters()}
+        where = {}
+        for i, g in enumerate(groups):
+            if tuple(g.get("betas", betas)) != betas or g.get("eps", eps) != eps:
+                raise ValueError(f"FusedAdamW: {label(i)} has betas {g.get('betas', betas)} / eps {g.get('eps', eps)}, the optimizer {betas} / {eps}: "
+                                 "one betas and one eps for all groups (lr and weight_decay may differ)")
+            for p in g["params"]:
+                if id(p) not in names:
+                    raise ValueError(f"FusedAdamW: {label(i)} holds a tensor of shape {tuple(p.shape)} that is not a parameter of the model")
+                if id(p) in where:
+                    raise ValueError(f"FusedAdamW: parameter {names[id(p)]!r} is in two groups, {label(where[id(p)])} and {label(i)}")
+                where[id(p)] = i
+        missing = [n for k, n in names.items() if k not in where]
+        if missing:
+            raise ValueError(f"FusedAdamW: parameter {missing[0]!r} is in no group ({len(missing)} in all; frozen parameters are listed too: "
+                             "requires_grad decides per step)")
+        return groups
 
     def _ensure(self):
         S = self.model.store
@@ -106,24 +143,32 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._m.copy_(pm)
                 self._v.copy_(pv)
                 self._pending = None
-            self._hp = torch.zeros(8, device=S.P.device)
+            self._hp = None
+        width = 8 + 2 * len(self.param_groups)   # the hp row of mvlt_adamw_step, then {lr, weight_decay} of every group: the table of mvlt_adamw_step_groups
+        if self._hp is None or self._hp.numel() != width:          # (the second: add_param_group)
+            self._hp = torch.zeros(width, device=S.P.device)
             # the step's scalars reach the device through a ring of PINNED rows: from a pageable source hipMemcpyAsync stages the copy on
             # the host and the call returns only when the stream has drained -- the host then enqueues the optimizer kernel and the whole
             # next forward behind an idle GPU (1.3 ms per fine-tune step, tools/host_time.py).  An event per row guards its reuse.
-            self._hp_pin = torch.zeros(4, 8).pin_memory() if S.P.is_cuda else None
+            self._hp_pin = torch.zeros(4, width).pin_memory() if S.P.is_cuda else None
             self._hp_ev = [None] * 4
         if self._pending_counts is not None:     # step counters of a checkpoint that was loaded before the first forward
             S._gate_buffers()[1].copy_(torch.tensor(self._pending_counts, dtype=torch.int32))
             self._pending_counts = None
-        key = (S.P.data_ptr(), tuple(p.requires_grad for p in S._plist))
+        key = (S.P.data_ptr(), tuple(p.requires_grad for p in S._plist), tuple(g["weight_decay"] != 0 for g in self.param_groups))
         if self._mask_key != key:                # the store was re-materialised, or a parameter was frozen / un-frozen (as FlatStore's norm mask)
-            # one byte per element: 1 = weight decay applies (timm's split: not for 1-D tensors / biases), 0 = it does not (alignment gaps too),
-            # 2 = the parameter is frozen: the kernel leaves it, its moments and its bf16 copy alone
-            ids_nd = {id(p) for p in self.param_groups[0]["params"]}
+            # one byte per element: 1 = weight decay applies (the parameter's group has a non-zero one; timm's split: not for 1-D tensors / biases), 0 = it
+            # does not (alignment gaps too), 2 = the parameter is frozen: the kernel leaves it, its moments and its bf16 copy alone
+            # ... and next to it the byte mvlt_adamw_step_groups reads: the index of the parameter's group, 255 for frozen parameters and alignment gaps
+            group_ix = {id(p): i for i, g in enumerate(self.param_groups) for p in g["params"]}
+            ids_nd = {k for k, i in group_ix.items() if not key[2][i]}
             mask = torch.zeros(S.total, dtype=torch.uint8)
+            group_of = torch.full((S.total,), ops.OPT_FROZEN, dtype=torch.uint8)
             runs = []
             for name, p in S.params.items():
                 off, n, _ = S.offsets[name]
+                if p.requires_grad:
+                    group_of[off:off + n] = group_ix[id(p)]
                 if not p.requires_grad:
                     mask[off:off + n] = ops.ADAMW_FROZEN
                     hi = off + (n + ALIGN - 1) // ALIGN * ALIGN
@@ -134,6 +179,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 elif id(p) not in ids_nd:
                     mask[off:off + n] = 1
             self._wd_mask = mask.to(S.P.device)
+            self._group_of = group_of.to(S.P.device)
             self._frozen_ranges = [(lo, hi) for lo, hi in runs]
             self._mask_key = key
         return S
@@ -147,15 +193,22 @@ class FusedAdamW(torch.optim.Optimizer):
         S = self._ensure()
         S.sync_grads()
         self._step += 1
-        g0, g1 = self.param_groups
+        groups = self.param_groups
+        g0 = groups[0]
         b1, b2 = g0["betas"]
-        assert g0["lr"] == g1["lr"], "FusedAdamW steps both param groups with one learning rate (as timm's scheduler sets them)"
+        # One learning rate and at most one non-zero weight decay (the default two groups under timm's scheduler, or the caller's groups when they agree):
+        # mvlt_adamw_step with the decay mask.  Anything else: mvlt_adamw_step_groups, which looks both up per element.
+        decays = {g["weight_decay"] for g in groups if g["weight_decay"] != 0}
+        uniform = len(decays) <= 1 and all(g["lr"] == g0["lr"] for g in groups)
+        wd = decays.pop() if uniform and decays else 0.0
         gscale, S.pending_grad_scale = S.pending_grad_scale, 1.0      # 1/world of the data-parallel mean, applied in the kernel
         clip, S.pending_clip = S.pending_clip, None                   # clip coefficient (device scalar) of FlatStore.clip_grad_norm: one more factor in the kernel
         gate, S.pending_gate = S.pending_gate, None                   # [norm, coef, ok, 0] of FlatStore.gate_grads: the gated kernel obeys ok and applies coef
         if gate is not None and clip is not None:
             raise RuntimeError("FusedAdamW: both a clip and a step gate are pending (FlatStore.gate_grads(max_norm) does the clipping itself)")
-        row = [g0["lr"], b1, b2, g0["eps"], g1["weight_decay"], 1 - b1 ** self._step, 1 - b2 ** self._step, gscale]
+        row = [g0["lr"], b1, b2, g0["eps"], wd, 1 - b1 ** self._step, 1 - b2 ** self._step, gscale]
+        for g in groups:                         # the table rides behind the row: one copy through the ring for both
+            row += (g["lr"], g["weight_decay"])
         if self._hp_pin is None:
             self._hp.copy_(torch.tensor(row, dtype=torch.float32))
         else:
@@ -168,6 +221,10 @@ class FusedAdamW(torch.optim.Optimizer):
             ev.record()
         for lo, hi in phased_ranges(S):
             if self._all_frozen(lo, hi):         # nothing in the range steps: no launch
+                continue
+            if not uniform:                      # (a pending gate: gate_grads waited for every collective, this is the single whole range)
+                ops.adamw_step_groups(S.P[lo:hi], S.G[lo:hi], self._m[lo:hi], self._v[lo:hi], None if S.C is None else S.C[lo:hi], hi - lo, self._hp,
+                                      self._group_of[lo:hi], self._hp[8:], len(groups), gscale_dev=clip, gate=gate)
                 continue
             if gate is not None:                 # (gate_grads waited for every collective: this is the single whole range)
                 ops.adamw_step_gated(S.P[lo:hi], S.G[lo:hi], self._m[lo:hi], self._v[lo:hi], None if S.C is None else S.C[lo:hi], hi - lo, self._hp,
@@ -236,6 +293,65 @@ class FusedAdamW(torch.optim.Optimizer):
                 else:
                     self._m = self._v = None
                     self._pending = (fused["m"].detach().clone(), fused["v"].detach().clone())
+
+
+_STAGE_NAME = re.compile(r"([A-Za-z_]+?)_?(\d+)")
+
+
+def layer_ids(model):
+    """{parameter name: layer id} for layer-wise lr decay down the pyramid -- a function of the parameter names and `model.depths` alone.  With
+    L = sum(depths):
+        0           the BERT embedding block (text_embeddings.*) and what stage 1 has in front of its blocks: patch_embed1, text_embed1, pos_embed1, text_pos_embed1
+        1 .. L      the blocks in forward order: block{s}.{j} has 1 + depths[0] + ... + depths[s - 2] + j
+        later stages' patch / text embeddings, position embeddings and any other tensor named <something>{s}: the id of block{s}.0, the first block they feed
+        norm{s}     a stage's closing norm: the id of the stage's last block
+        L + 1       every head (a top-level name with `head` in it: mlm_head*, itm_head*, sup_cls_head*, sub_cls_head*, t2i_head -- the MIM decoder)
+    A name that fits none of these raises ValueError: a new part of the model gets a deliberate id, not the heads' learning rate by default."""
+    m = _unwrap(model)
+    depths = tuple(m.depths)
+    first = [1 + sum(depths[:s]) for s in range(len(depths))]           # id of block{s + 1}.0
+    ids = {}
+    for name, _ in m.named_parameters():
+        top, _, rest = name.partition(".")
+        st = _STAGE_NAME.fullmatch(top)
+        stage = int(st.group(2)) if st else 0
+        if top == "text_embeddings":
+            ids[name] = 0
+        elif "head" in top:
+            ids[name] = sum(depths) + 1
+        elif st is None or not 1 <= stage <= len(depths):
+            raise ValueError(f"layer_ids: no layer id for parameter {name!r} (not an embedding, a stage-numbered tensor, a block or a head)")
+        elif st.group(1) == "block":
+            j = int(rest.partition(".")[0])
+            if not 0 <= j < depths[stage - 1]:
+                raise ValueError(f"layer_ids: {name!r} names block {j} of stage {stage}, which has {depths[stage - 1]}")
+            ids[name] = first[stage - 1] + j
+        elif st.group(1) == "norm":
+            ids[name] = first[stage - 1] + depths[stage - 1] - 1
+        else:
+            ids[name] = 0 if stage == 1 else first[stage - 1]
+    return ids
+
+
+def layer_decay_groups(model, lr, weight_decay, layer_decay):
+    """Parameter groups for FusedAdamW(model, param_groups=...) (or any torch optimizer) with layer-wise lr decay: the group of layer id i (`layer_ids`) gets
+    lr * layer_decay ** (L + 1 - i), so the heads train at `lr` and the embeddings at lr * layer_decay ** (L + 1).  Every layer is split by timm's no-decay
+    rule (1-D tensors and `.bias`: weight_decay 0), empty halves are left out: at most 2 * (L + 2) groups, ordered by layer id, no-decay half first.  Each
+    group carries `name` ("layer_<i>_decay" / "layer_<i>_no_decay") and `lr_scale` for logging; frozen parameters are listed like the others.  A scheduler that
+    scales each group from its own base lr (sched.CosineLRScheduler) keeps the ratios."""
+    m = _unwrap(model)
+    ids = layer_ids(m)
+    top = sum(m.depths) + 1
+    split = {}
+    for name, p in m.named_parameters():
+        no_decay = p.dim() == 1 or name.endswith(".bias")
+        split.setdefault((ids[name], 0 if no_decay else 1), []).append(p)
+    groups = []
+    for (i, dec), params in sorted(split.items(), key=lambda kv: kv[0]):
+        scale = layer_decay ** (top - i)
+        groups.append(dict(params=params, lr=lr * scale, weight_decay=weight_decay if dec else 0.0, lr_scale=scale,
+                           name=f"layer_{i}_{'decay' if dec else 'no_decay'}"))
+    return groups
 
 
 class FusedModelEma:

@@ -10,7 +10,8 @@ here by closed-form values (tests/test_host_cpu.py):
     epoch >= epochs        : lr = min_lr                                                                  (the cool-down epochs)
 
 `num_epochs` = epochs + cooldown_epochs is what create_scheduler returns as the run length.  Works on any torch optimizer, including
-FusedAdamW (both parameter groups get the same lr, which its kernel requires).
+FusedAdamW: every parameter group is scaled from its own base lr, so the default two groups keep one lr and groups built with
+different rates (optim.layer_decay_groups) keep theirs through warm-up, cosine and cool-down.
 """
 import math
 
