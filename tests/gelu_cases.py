@@ -203,12 +203,13 @@ def half_ulp_bf16(v):
 
 
 def bar(form, what, h, r, rows, *, rounded):
-    """the bound of one activation per element: h, r float64 [R, n] (input and float64 reference), rows the sweep row of each row of h.
+    """the bound of one activation per element: h, r float64 [R, n] (input and float64 reference), rows the sweep row of each row of h (None: the worst row for all).
     SLOP x E_row x (|h| for GELU, 1 for GELU') + half a bf16 ulp where the kernel rounds + ABS x max(1, |r|).  The half ulp is that of |r| + the rest of the bar, not
     of r alone: the kernel rounds ITS value, which may lie across a power of two from r (up to twice the half ulp of r just under a power of two, and in the tiny
     binades where ABS is all of the bar; docs/gelu_range.md names this as the one departure from the formula the tests were specified with)."""
     e = errors(form)
-    E = (e.phi if what == "g" else e.dg)[list(rows)][:, None]
+    E = e.phi if what == "g" else e.dg
+    E = E.max() if rows is None else E[list(rows)][:, None]  # rows None: an input that is no sweep value (the integer pre-activations of the 8-phase position case) takes the form's worst row
     b = SLOP * E * (h.abs() if what == "g" else torch.ones_like(h)) + ABS * r.abs().clamp(min=1.0)
     if rounded:
         b = b + half_ulp_bf16(r.abs() + b)
@@ -330,3 +331,198 @@ def gemm_case(N, K=8, j0=0):
 def h_of(c):
     """the pre-activations a case's operands give, in float64 (b1 = 0)"""
     return c.x @ c.w1.t()
+
+
+# ---------------------------------------------------------------------------------------------------------------- the 8-phase NT GEMM epilogues (tests/test_gelu_p8_gpu.py)
+# gemm_nt_p8_kernel<3 | 4, 4 | 3, 2, 2, false> compiles nt_epilogue_lean<128, EPI, TM = 8 | 6, NWN = 4, FULL = true>: 2 x 4 waves, a wave tile of (16 TM) x 64, walked in
+# TM / 2 = 4 | 3 halves of 32 rows; a lane owns the 8 columns `n0 + 64 wn + 8 (lane % 8)` and the rows `... + 32 half + 8 it + lane / 8`.  The launches are as large as
+# the plan's smallest 8-phase shapes, so nothing of M x N elements lives on the host: every expectation is a small TABLE (the 67 x 128 sweep, or the integers) and an
+# index u[m][n] into it, built where the output lives.  The functions below take a device for that reason and run on the CPU just the same.
+P8_N = 2048
+P8_M = {256: 6400, 192: 4608}                                # tile height -> rows: 200 tiles of 256 x 256, 192 tiles of 192 x 256 (the smallest counts the plan takes)
+P8_KERNEL = {256: "gemm_nt_p8_kernel<%d, 4, 2, 2, false>", 192: "gemm_nt_p8_kernel<%d, 3, 2, 2, false>"}
+P8_BATCH = {256: (5, 1280), 192: (6, 768)}                   # batches x rows per batch of the layout case
+NFLAT = NROWS * 128
+INT_LIM = 256
+BIAS2 = {5: 0.5, 70: -1.5, 131: 2.0, 200: -3.0, 1031: 0.75, 2047: 1.0}      # act 2: one column in every wave column, the first and the last lane chunk; no entry cancels a power of two
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_table(form="poly"):
+    """the sweep laid flat (u = 128 row + column): inputs, float64 references and bars.  bar_dg is the GELU' bar BEFORE the product with the accumulator and its rounding."""
+    h, rows = sweep(128), list(range(NROWS))
+    g, dg = exact(h)
+    loose = torch.zeros(NROWS, 128, dtype=torch.bool)
+    loose[list(DENORMAL_ROWS)] = True
+    return NS(h=h.flatten(), g=g.flatten(), dg=dg.flatten(), bar_g=bar(form, "g", h, g, rows, rounded=True).flatten(),
+              bar_dg=bar(form, "dg", h, dg, rows, rounded=False).flatten(), loose=loose.flatten())
+
+
+@functools.lru_cache(maxsize=None)
+def int_table(form="poly"):
+    """the integers -256 .. 256 (u = h + 256), each a bf16 value: the worst sweep row's E for all of them"""
+    h = torch.arange(-INT_LIM, INT_LIM + 1).double()[None, :]
+    g, dg = exact(h)
+    return NS(h=h.flatten(), g=g.flatten(), dg=dg.flatten(), bar_g=bar(form, "g", h, g, None, rounded=True).flatten(),
+              bar_dg=bar(form, "dg", h, dg, None, rounded=False).flatten(), loose=torch.zeros(2 * INT_LIM + 1, dtype=torch.bool))
+
+
+def grid(M, N, dev="cpu"):
+    return torch.arange(M, device=dev)[:, None], torch.arange(N, device=dev)[None, :]
+
+
+def u_tiled(m, n):
+    """the sweep tiled over the output: 67 is coprime to every tile dimension"""
+    return (m % NROWS) * 128 + n % 128
+
+
+def u_hash(m, n):
+    """a sweep value per (m, n) with no period in either index (the product terms break every row / column period)"""
+    return (m * 7919 + n * 104729 + (m // 7) * (n // 5) + (m * n) % 8191) % NFLAT
+
+
+def u_bias(n, rep):
+    """the main sweep value of column n in launch `rep` of four: (37 n + 11) mod 2048 runs through a quarter of the 64 x 128 values laid flat, 64 columns on are 10 rows
+    (binades) on, 128 columns 20"""
+    return ((37 * n + 11) % 2048) * 4 + rep
+
+
+def pm1(shape, seed, density=0.22):
+    """entries in {-1, 0, 1}, half the density each sign, from a seeded generator"""
+    r = torch.rand(shape, generator=torch.Generator().manual_seed(seed), dtype=F64)
+    return (r < density / 2).double() - (r >= 1 - density / 2).double()
+
+
+POSITION_SEED = 20
+
+
+def p8_sweep_case(BM, M=None, K=128):
+    """cases 1 and 2.  act 1: A[m][0] = a_(m mod 67), B[n][0] = w_(n mod 128): h = the tiled sweep.  act 2: A2[m][1] = 2^(m mod 3), B2[n][1] = 2^-(n mod 5): the
+    accumulator is a power of two that names its row AND its column; H = the tiled sweep from the host; bias2 = BIAS2 (or none)."""
+    M, N = M or P8_M[BM], P8_N
+    A, B, A2, B2 = (torch.zeros(r, K, dtype=F64) for r in (M, N, M, N))
+    A[:, 0] = row_values()[torch.arange(M) % NROWS]
+    B[:, 0] = col_values(N)
+    A2[:, 1] = 2.0 ** (torch.arange(M) % 3).double()
+    B2[:, 1] = 2.0 ** -(torch.arange(N) % 5).double()
+    bias2 = torch.zeros(N, dtype=F64)
+    for n, v in BIAS2.items():
+        bias2[n] = v
+    return NS(BM=BM, M=M, N=N, K=K, A=A, B=B, bias=None, A2=A2, B2=B2, bias2=bias2, t1=sweep_table(), t2=sweep_table(), u1=lambda dev="cpu": u_tiled(*grid(M, N, dev)),
+              u2=lambda dev="cpu": u_tiled(*grid(M, N, dev)))
+
+
+def p8_bias_case(BM, rep, M=None, K=128):
+    """case 3, act 1 only: A = 0 and bias[n] = the main sweep value u_bias(n, rep), the same in every row"""
+    M, N = M or P8_M[BM], P8_N
+    n = torch.arange(N)
+    return NS(BM=BM, M=M, N=N, K=K, A=torch.zeros(M, K, dtype=F64), B=col_values(N)[:, None].repeat(1, K), bias=sweep_table().h[u_bias(n, rep)], t1=sweep_table(),
+              u1=lambda dev="cpu": u_bias(grid(M, N, dev)[1], rep) + 0 * grid(M, N, dev)[0])
+
+
+def p8_position_case(BM, M=None, K=192):
+    """case 4: A, B in {-1, 0, 1} through three k-tiles.  act 1: h = A B^T, an integer and a bf16 value.  act 2: the same product as the accumulator, H = a sweep value
+    per (m, n) by u_hash"""
+    M, N = M or P8_M[BM], P8_N
+    A, B = pm1((P8_M[BM], K), POSITION_SEED)[:M], pm1((N, K), POSITION_SEED + 1)
+
+    def u1(dev="cpu"):
+        return (A.to(dev) @ B.to(dev).t()).round().long() + INT_LIM
+    return NS(BM=BM, M=M, N=N, K=K, A=A, B=B, bias=None, A2=A, B2=B, bias2=None, t1=int_table(), t2=sweep_table(), u1=u1, u2=lambda dev="cpu": u_hash(*grid(M, N, dev)))
+
+
+def to_bf16(t):
+    return t.float().to(BF).double()
+
+
+def compare_at(got, want, bound, h, what):
+    """`compare` where the output lives: everything on got's device, only a failure's first elements travel.  Returns the worst error / bound (0 / 0 counts as 0)."""
+    assert got.shape == want.shape == bound.shape == h.shape, (what, got.shape, want.shape, bound.shape, h.shape)
+    g = got.double()
+    err = (g - want).abs()
+    bad = ~(err <= bound)
+    if bool(bad.any()):
+        idx = bad.nonzero()[:6].cpu()
+        first = [(int(r), int(k), float(h[r, k]), float(g[r, k]), float(want[r, k])) for r, k in idx.tolist()]
+        raise OverBar(f"{what}: {int(bad.sum())} of {bad.numel()} elements over their bar; first (row, col, h, got, want): {first}", first)
+    return float(torch.where(bound > 0, err / bound.clamp(min=1e-300), torch.zeros_like(err)).max())
+
+
+def p8_check_h(c, H, what):
+    """act 1: the stored pre-activation equals the table's value bit for bit (check_h's rule for the denormal row: below ABS instead)"""
+    t, u = c.t1, c.u1(H.device)
+    want, loose = t.h.to(H.device)[u], t.loose.to(H.device)[u]
+    got = H.double()
+    assert bool(((got == want) | loose).all()), f"{what}: the stored pre-activation is not h"      # (as in check_h, the -0 row may come back +0: 0 + -0 in the accumulator)
+    assert not bool(loose.any()) or float(got[loose].abs().max()) <= ABS, what
+
+
+def p8_check_act1(c, C, what):
+    """C against the float64 exact-erf GELU of the table's value under its bar"""
+    t, u = c.t1, c.u1(C.device)
+    return compare_at(C, t.g.to(C.device)[u], t.bar_g.to(C.device)[u], t.h.to(C.device)[u], what)
+
+
+def p8_check_act2(c, C, what, bias=None):
+    """C against (acc + bias) GELU'(h) in float64: |acc + bias| times the GELU' bar of h, plus half a bf16 ulp of the result (taken, as in `bar`, at |result| + the rest)"""
+    dev = C.device
+    t, u = c.t2, c.u2(dev)
+    acc = c.A2.to(dev) @ c.B2.to(dev).t()
+    if bias is not None:
+        acc = acc + bias.to(dev)[None, :]
+    want = acc * t.dg.to(dev)[u]
+    b = acc.abs() * t.bar_dg.to(dev)[u]
+    return compare_at(C, want, b + half_ulp_bf16(want.abs() + b), t.h.to(dev)[u], what)
+
+
+# ---- what a wrong epilogue would store: the form as it stands on operands that took a wrong turn (tests/test_gelu_cases_cpu.py applies each move to every case)
+P8_MOVES = ("slot1", "slot2", "chunk64", "chunk128", "bias_wave", "rows16", "bias_order")
+
+
+def p8_rows(M, BM, move):
+    """the row a row's operand comes from"""
+    m = torch.arange(M)
+    if move == "rows16":                                     # rows r and r + 16 of a staged 32-row half exchanged
+        return m ^ 16
+    if move in ("slot1", "slot2"):                           # the prefetch slots: half h processed with the H requested for half h + 1 | h + 2 (among the wave's TM / 2)
+        W = BM // 2
+        r = m % BM
+        rr = r % W
+        return m - r + (r // W) * W + ((rr // 32 + int(move[-1])) % (W // 32)) * 32 + rr % 32
+    return m
+
+
+def p8_cols(N, move):
+    """the column a column's operand comes from"""
+    n = torch.arange(N)
+    c = n % 256
+    if move in ("chunk64", "chunk128"):                      # one lane chunk (columns 88 .. 95 of every tile: wave column 1, lane chunk 3) addressed 64 | 128 columns on
+        return torch.where((c >= 88) & (c < 96), n - c + (c + int(move[5:])) % 256, n)
+    if move == "bias_wave":                                  # the bias chunk of the next wave column
+        return n - c + (c + 64) % 256
+    return n
+
+
+def p8_model(c, act, move=None, bias=None, form="poly"):
+    """(C, H) as the epilogue stores them (the restated form, products and sums rounded as fp32 does, then bf16), with one `move` applied.  bias_order: GELU taken of the
+    value BEFORE the bias, which is added behind it (act 2: the bias added behind the product)."""
+    acc = (c.A @ c.B.t()) if act == 1 else (c.A2 @ c.B2.t())
+    b = torch.zeros(c.N, dtype=F64) if bias is None else bias
+    if move == "rows16":
+        acc = acc[p8_rows(c.M, c.BM, move)]
+    if move == "bias_wave":
+        b = b[p8_cols(c.N, move)]
+    if act == 1:
+        pre = (acc + b).float().double()
+        H = to_bf16(pre)
+        C = emulate(form, acc)[0] + b if move == "bias_order" else emulate(form, pre)[0]
+    else:
+        H = to_bf16(c.t2.h[c.u2()])
+        if move in ("slot1", "slot2"):
+            H = H[p8_rows(c.M, c.BM, move)]
+        dg = emulate(form, H)[1]
+        C = acc * dg + b if move == "bias_order" else (acc + b) * dg
+    C = to_bf16(C)
+    if move in ("chunk64", "chunk128"):
+        C, H = C[:, p8_cols(c.N, move)], H[:, p8_cols(c.N, move)]
+    return C, H

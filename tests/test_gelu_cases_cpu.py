@@ -1,6 +1,8 @@
 """CPU: the premises of tests/test_gelu_range_gpu.py (tests/gelu_cases.py; docs/gelu_range.md).  The sweep is complete and bf16-exact, every one-hot construction
 isolates exactly one activation per observed element, the restated forms meet their design bounds, and the comparison notices what a subtly wrong kernel does."""
 import math
+import os
+import re
 
 import pytest
 import torch
@@ -181,3 +183,141 @@ def test_perturbed_forms_fail(form, what, v, lanes, rounded):
     if v == "clamp4":                                                  # the overshoot shows where common.h says: from |h| = 4 on
         row, col, hh, got, want = e.value.first[0]
         assert math.isfinite(got) and abs(hh) >= 4
+
+
+# ================================================================== the 8-phase NT GEMM epilogues (tests/test_gelu_p8_gpu.py)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TILES = sorted(gc.P8_M)
+
+
+def source(name):
+    return open(os.path.join(ROOT, "mvlt_amd", name)).read()
+
+
+def test_p8_epilogues_compile_the_polynomials():
+    """EPI 3 / 4 of nt_epilogue_lean call gelu_fast2 / gelu_fast_grad2, which are gelu_poly1 / gelu_poly_grad1 under MVLT_GELU_POLY bits 1 / 0; the default is 3 and
+    neither the build nor the 8-phase translation unit sets another: the bars of the 8-phase cases are the `poly` ones"""
+    common, epi, p8 = source("csrc/common.h"), source("csrc/gemm_common.h"), source("csrc/gemm_nt_p8.hip")
+    assert re.search(r"#ifndef MVLT_GELU_POLY\n#define MVLT_GELU_POLY 3\n#endif", common)
+    assert re.search(r"f32x2 gelu_fast2\(f32x2 x\) \{\n#if MVLT_GELU_POLY & 2\n  return f32x2\{gelu_poly1\(x\[0\]\), gelu_poly1\(x\[1\]\)\};\n#endif", common)
+    assert re.search(r"f32x2 gelu_fast_grad2\(f32x2 x\) \{\n#if MVLT_GELU_POLY & 1\n  return f32x2\{gelu_poly_grad1\(x\[0\]\), gelu_poly_grad1\(x\[1\]\)\};\n#endif", common)
+    lean = epi[epi.index("void nt_epilogue_lean("):epi.index("void nt_epilogue_192(")]
+    assert re.search(r"if \(EPI == 3\) \{\n\s+if \(p\.H\) store8\(p\.H, v\);[^}]*gelu_fast2\(", lean) and re.search(r"if \(EPI == 4\) \{[^}]*gelu_fast_grad2\(f32x2\{o8\[e\]", lean)
+    assert "gelu_erf" not in lean and "MVLT_GELU_POLY" not in p8 and "MVLT_GELU_POLY" not in source("build.py")
+    assert "nt_epilogue_lean<128, EPI, WMT, 4, EPI != 2 && !RAG>" in p8                  # NWN = 4, FULL = true for EPI 3 / 4 of the whole-tile instantiations
+
+
+@pytest.mark.parametrize("BM", TILES)
+def test_p8_sweep_operands_and_tile_coverage(BM):
+    """cases 1 and 2: one product per element, equal to the tiled sweep; the act 2 accumulator is 2^(m mod 3 - n mod 5) and stays a non-zero fp32 value with the bias.
+    Every 32-row half of a wave row x 128-column half of a tile (the unit the epilogue stages and the period of the mantissas) sees every value of the sweep -- all
+    8192 bf16 values of the 32 binades and the three extra rows -- and every row position of a tile sees as many different sweep rows as there are row tiles"""
+    c = gc.p8_sweep_case(BM)
+    M, N = c.M, c.N
+    assert (M, N) == (gc.P8_M[BM], 2048) and M % BM == 0 and N % 256 == 0 and (M // BM) * (N // 256) >= 192
+    assert gc.bf16_exact(c.A) and gc.bf16_exact(c.B) and gc.bf16_exact(c.A2) and gc.bf16_exact(c.B2)
+    assert not bool(c.A[:, 1:].any()) and not bool(c.B[:, 1:].any()) and not bool(c.A2[:, 0].any()) and not bool(c.A2[:, 2:].any()) and not bool(c.B2[:, 2:].any())
+    u = c.u1()
+    assert u.shape == (M, N) and torch.equal(c.A @ c.B.t(), c.t1.h[u]) and torch.equal(u, c.u2())
+    m, n = gc.grid(M, N)
+    acc = c.A2 @ c.B2.t()
+    assert torch.equal(acc, 2.0 ** ((m % 3) - (n % 5)).double())
+    assert len({(a, b) for a in range(3) for b in range(5)}) == 15 and math.gcd(3, 32) == math.gcd(5, 8) == 1       # the row AND the column name the accumulator
+    withb = acc + c.bias2
+    assert int((c.bias2 != 0).sum()) == len(gc.BIAS2) and bool((withb != 0).all()) and torch.equal(withb.float().double(), withb)
+    assert {k % 256 // 64 for k in gc.BIAS2} == {0, 1, 2, 3} and {k % 64 // 8 for k in gc.BIAS2} >= {0, 7}
+    full = set(range(gc.NFLAT))
+    for rc in range(BM // 32):
+        rows = ((m[:, 0] % BM) // 32 == rc).nonzero()[:, 0]
+        for cc in range(2):
+            cols = ((n[0] % 256) // 128 == cc).nonzero()[:, 0]
+            assert set(u[rows][:, cols].unique().tolist()) == full, (rc, cc)
+    want = bits(gc.sweep(128)[:gc.NMAIN]).flatten().tolist()
+    assert sorted(bits(c.t1.h[:gc.NMAIN * 128]).tolist()) == sorted(want) and len(set(want)) == 8192
+    for r in range(BM):
+        assert len(set((u[r::BM, 0] // 128).tolist())) == M // BM
+
+
+@pytest.mark.parametrize("BM", TILES)
+def test_p8_bias_operands(BM):
+    """case 3: the four launches carry every one of the 8192 main values exactly once, each an fp32 value; a column's value has no period of 64 or 128 columns"""
+    seen = []
+    for rep in range(4):
+        c = gc.p8_bias_case(BM, rep)
+        assert not bool(c.A.any()) and gc.bf16_exact(c.bias) and c.bias.shape == (c.N,)
+        u = c.u1()
+        assert u.shape == (c.M, c.N) and bool((u == u[0]).all()) and torch.equal(c.t1.h[u[0]], c.bias)
+        for period in (64, 128):
+            assert not bool((c.bias[period:] == c.bias[:-period]).any())
+        seen += u[0].tolist()
+    assert sorted(seen) == list(range(gc.NMAIN * 128))
+
+
+@pytest.mark.parametrize("BM", TILES)
+def test_p8_position_operands(BM):
+    """case 4, the two conditions of the fixed seed: |h| <= 256 everywhere (h indexes the integer table) and at least half of the elements in 1 <= |h| <= 4, where
+    GELU separates neighbouring integers by far more than a bar; the hash of act 2 reaches every sweep value and repeats with no row or column period"""
+    c = gc.p8_position_case(BM)
+    assert set(c.A.unique().tolist()) == set(c.B.unique().tolist()) == {-1.0, 0.0, 1.0} and c.K == 192 and c.A.shape == (gc.P8_M[BM], 192)
+    h = c.A @ c.B.t()
+    mag = h.abs()
+    assert float(mag.max()) <= gc.INT_LIM and torch.equal(h, h.round()) and gc.bf16_exact(h)
+    assert float(((mag >= 1) & (mag <= 4)).double().mean()) >= 0.5
+    assert torch.equal(c.t1.h[c.u1()], h)
+    t = gc.int_table()
+    near = (t.h >= -3) & (t.h <= 5)                                                     # (GELU(-4) and GELU(-5) are both 1e-4 from 0: no more than a bar apart)
+    assert bool(((t.g[1:] - t.g[:-1]).abs()[near[1:] & near[:-1]] > 8 * t.bar_g[1:][near[1:] & near[:-1]]).all())
+    u = c.u2()
+    assert set(u.unique().tolist()) == set(range(gc.NFLAT))
+    for p in (1, 16, 32, 64, 67, 128, 256):
+        assert float((u[p:] == u[:-p]).double().mean()) < 0.01 and float((u[:, p:] == u[:, :-p]).double().mean()) < 0.01, p
+
+
+def p8_cases(BM):
+    """(name, case, act, bias) of cases 1-4 on ONE row of tiles: the rows 0 .. BM - 1 of the launched case, which hold every position of a tile"""
+    sw, pos = gc.p8_sweep_case(BM, BM), gc.p8_position_case(BM, BM)
+    out = [("1 sweep act 1", sw, 1, None), ("2 sweep act 2", sw, 2, None), ("2 sweep act 2 + bias", sw, 2, sw.bias2)]
+    out += [(f"3 bias only {rep}", c, 1, c.bias) for rep in (0, 3) for c in (gc.p8_bias_case(BM, rep, BM),)]
+    return out + [("4 position act 1", pos, 1, None), ("4 position act 2", pos, 2, None)]
+
+
+def p8_run(c, act, bias, move, name):
+    C, H = gc.p8_model(c, act, move, bias)
+    if act == 1:
+        return gc.p8_check_act1(c, C, name)
+    return gc.p8_check_act2(c, C, name, bias)
+
+
+@pytest.mark.parametrize("BM", TILES)
+def test_p8_models_as_they_stand_pass(BM):
+    for name, c, act, bias in p8_cases(BM):
+        assert p8_run(c, act, bias, None, name) <= 1.0
+        if act == 1:
+            gc.p8_check_h(c, gc.p8_model(c, act, None, bias)[1], name)
+
+
+# the cases that must notice each move (asserted exactly: a case that is blind to a move is named by its absence)
+ALL_ACT2 = ("2 sweep act 2", "2 sweep act 2 + bias", "4 position act 2")
+CAUGHT_BY = {
+    "slot1": ALL_ACT2, "slot2": ALL_ACT2,                                                # (act 1 prefetches nothing)
+    "chunk64": ("1 sweep act 1",) + ALL_ACT2 + ("3 bias only 0", "3 bias only 3", "4 position act 1"),
+    "chunk128": ALL_ACT2 + ("3 bias only 0", "3 bias only 3", "4 position act 1"),       # (the rank-one sweep of act 1 repeats every 128 columns)
+    "bias_wave": ("2 sweep act 2 + bias", "3 bias only 0", "3 bias only 3"),
+    "rows16": ("1 sweep act 1",) + ALL_ACT2 + ("4 position act 1",),                     # (the bias-only rows are all alike)
+    "bias_order": ("2 sweep act 2 + bias", "3 bias only 0", "3 bias only 3"),
+}
+
+
+@pytest.mark.parametrize("move", gc.P8_MOVES)
+@pytest.mark.parametrize("BM", TILES)
+def test_p8_moves_are_caught(BM, move):
+    """the moves a wrong epilogue would make -- the two prefetch slots exchanged, a lane chunk addressed 64 / 128 columns on, the bias chunk of the neighbouring wave
+    column, rows r and r + 16 of a staged half exchanged, GELU on the wrong side of the bias -- applied to the restated form: each is over its bar in the named cases"""
+    caught = []
+    for name, c, act, bias in p8_cases(BM):
+        try:
+            p8_run(c, act, bias, move, name)
+        except gc.OverBar as e:
+            assert len(e.first[0]) == 5
+            caught.append(name)
+    assert caught and sorted(caught) == sorted(CAUGHT_BY[move]), (move, caught)

@@ -299,6 +299,29 @@ def test_nt_thresholds(below, above, k_below, k_above):
         assert _plan(_args(rec))[1] == rec["out"]["kernel"]
 
 
+@pytest.mark.parametrize("M, K, extra, tile", [
+    # the smallest whole-tile shapes of the GELU / GELU' epilogues on the 8-phase kernels (tests/test_gelu_p8_gpu.py): 200 tiles of 256 x 256, 192 tiles of 192 x 256
+    (6400, 128, {}, "4, 2, 2"), (6400, 192, {}, "4, 2, 2"), (4608, 128, {}, "3, 2, 2"), (4608, 192, {}, "3, 2, 2"), (6144, 128, {}, "3, 2, 2"),
+    # ... with a bias, and in the layout of the strided case: lda = ldb = K + 8, ldc = N + 8, batch-strided output rows
+    (6400, 128, dict(bias=0), "4, 2, 2"), (4608, 128, dict(bias=0), "3, 2, 2"),
+    (6400, 192, dict(lda=200, ldb=200, ldc=2056, c_map=[0, 1280, 1320, 24, 0, 0, 0, 0, 0, 0, 0]), "4, 2, 2"),
+    (4608, 192, dict(lda=200, ldb=200, ldc=2056, c_map=[0, 768, 808, 24, 0, 0, 0, 0, 0, 0, 0]), "3, 2, 2"),
+])
+def test_nt_8_phase_gelu_shapes(M, K, extra, tile):
+    """act 1 (with the pre-activation stored) and act 2 at N = 2048: EPI 3 / 4 of the whole-tile 8-phase instantiations, one workgroup per tile in whole XCD groups"""
+    for act, epi in ((1, 3), (2, 4)):
+        p, name = _plan(_args({**_nt(M, 2048, K, act=act, H=0), **extra}))
+        assert name == f"gemm_nt_p8_kernel<{epi}, {tile}, false>", (M, K, act, name)
+        bm = 256 if tile[0] == "4" else 192
+        assert list(p.grid) == [8 * -(-(M // bm) // 8) * 8, 1, 1] and p.block == 512
+    # one k-tile less (K below 128), and one row tile less than 192 tiles of 192 x 256: the 128-wide kernel.  (Below 6400 rows the 256 x 256 tile has fewer than
+    # 200 tiles only at 6144 rows, which are one round of 192 x 256 tiles.)
+    for act in (1, 2):
+        assert _plan(_args({**_nt(M, 2048, 64, act=act, H=0), **extra, "lda": 64, "ldb": 64}))[1].startswith(f"gemm_nt_dma_kernel<128, 0, {2 + act}, ")
+        if M == 4608 and "c_map" not in extra:
+            assert _plan(_args({**_nt(M - 192, 2048, K, act=act, H=0), **extra}))[1].startswith(f"gemm_nt_dma_kernel<128, 0, {2 + act}, ")
+
+
 @pytest.mark.parametrize("atomics, partial", [
     # part_min: 7 / 8 m-splits meeting on 128 x 128 outputs
     (dict(M=3584, N1=128, splits=7, partials=0), dict(M=3584, N1=128, splits=8, partials=0)),
