@@ -1,4 +1,4 @@
-"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h, include/mvlt_hip_ema.h, include/mvlt_hip_plan.h and include/mvlt_hip_opt.h).
+"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h, include/mvlt_hip_ema.h, include/mvlt_hip_plan.h, include/mvlt_hip_opt.h and include/mvlt_hip_lamb.h).
 
 The product path has NO fallback: importing this module without the built library, or calling an op without a
 GPU, raises.  torch is used only for device memory and streams.
@@ -288,6 +288,25 @@ for _name, (_res, _args) in OPT_PROTOTYPES.items():
 OPT_VERSION = 1          # include/mvlt_hip_opt.h MVLT_OPT_VERSION this binding was written against
 if lib.mvlt_opt_version() != OPT_VERSION:
     raise ImportError(f"optimizer entry points mismatch: {LIB_PATH} is version {lib.mvlt_opt_version()}, the binding is version {OPT_VERSION} (stale build? run python -m mvlt_amd.build)")
+
+# The entry points of include/mvlt_hip_lamb.h (LAMB: layer-wise trust ratios over the flat store in three launches, docs/lamb.md): a table of their own,
+# bound and version-checked like the one above (tests/test_lamb_cpu.py compares it with that header).
+LAMB_PROTOTYPES = {
+    "mvlt_lamb_version": (_i, []),
+    "mvlt_lamb_check_tables": (_i, [_vp, _i, _vp, _i, _l, _i]),                                          # both tables: HOST arrays
+    "mvlt_lamb_moments": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),    # tensors / chunks: DEVICE arrays from here on
+    "mvlt_lamb_fold": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "mvlt_lamb_apply": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+}
+for _name, (_res, _args) in LAMB_PROTOTYPES.items():
+    if not hasattr(lib, _name):
+        raise ImportError(f"{LIB_PATH} does not export {_name} (include/mvlt_hip_lamb.h): stale build? run python -m mvlt_amd.build")
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
+LAMB_VERSION = 1         # include/mvlt_hip_lamb.h MVLT_LAMB_VERSION this binding was written against
+if lib.mvlt_lamb_version() != LAMB_VERSION:
+    raise ImportError(f"LAMB entry points mismatch: {LIB_PATH} is version {lib.mvlt_lamb_version()}, the binding is version {LAMB_VERSION} (stale build? run python -m mvlt_amd.build)")
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 

@@ -351,6 +351,65 @@ def adamw_step_groups(p, g, m, v, p16, n, hp, group_of, table, n_groups, *, gsca
                                        stream_ptr()), "mvlt_adamw_step_groups")
 
 
+LAMB_CHUNK = 16384        # elements one workgroup of lamb_moments / lamb_apply works on (MVLT_LAMB_CHUNK in include/mvlt_hip_lamb.h)
+LAMB_ROW = 6              # int64 per tensor row: offset, length, group, frozen, first_chunk, n_chunks (MVLT_LAMB_ROW)
+LAMB_ALWAYS_ADAPT = 1     # flags of lamb_fold (MVLT_LAMB_ALWAYS_ADAPT, MVLT_LAMB_TRUST_CLIP)
+LAMB_TRUST_CLIP = 2
+
+
+def lamb_check_tables(tensors, chunks, n, n_groups):
+    """The two tables of the LAMB launches as HOST tensors (int64 [n_tensors, LAMB_ROW], int32 [n_chunks, 2]) against buffers of n elements and n_groups
+    groups: raises MVLTError naming the first row that points outside them, overlaps, or does not tile the chunk table.  No device, no launch."""
+    assert tensors.dtype == torch.int64 and chunks.dtype == torch.int32 and not tensors.is_cuda and not chunks.is_cuda
+    assert tensors.is_contiguous() and chunks.is_contiguous() and tensors.numel() % LAMB_ROW == 0 and chunks.numel() % 2 == 0
+    check(L.lib.mvlt_lamb_check_tables(tensors.data_ptr() or None, tensors.numel() // LAMB_ROW, chunks.data_ptr() or None, chunks.numel() // 2, n, n_groups),
+          "mvlt_lamb_check_tables")
+
+
+def _lamb_tables_ok(tensors, chunks):
+    assert tensors.dtype == torch.int64 and tensors.is_contiguous() and tensors.numel() % LAMB_ROW == 0
+    assert chunks.dtype == torch.int32 and chunks.is_contiguous() and chunks.numel() % 2 == 0
+    return tensors.numel() // LAMB_ROW, chunks.numel() // 2
+
+
+def lamb_moments(p, g, m, v, n, hp, tensors, chunks, table, n_groups, partials, *, gscale_dev=None, gate=None):
+    """LAMB launch 1 (include/mvlt_hip_lamb.h): per chunk of one tensor, m and v stepped in `adamw_step`'s bits and partials[c] = {sum p^2, sum u^2}.  hp: the
+    fp32[8] row of `adamw_step`, slots 0 and 4 ignored; table: fp32 [n_groups, 2] = {lr, weight_decay}; tensors / chunks: the device copies of tables that
+    `lamb_check_tables` accepted for n.  gscale_dev as for `adamw_step`, gate as for `adamw_step_gated`; at most one."""
+    nt, nc = _lamb_tables_ok(tensors, chunks)
+    for t in (p, g, m, v, hp, table, partials):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert min(p.numel(), g.numel(), m.numel(), v.numel()) >= n and hp.numel() >= 8 and table.numel() >= 2 * n_groups and partials.numel() >= 2 * nc
+    assert gscale_dev is None or gscale_dev.dtype == torch.float32
+    assert gate is None or (gate.dtype == torch.float32 and gate.numel() >= 4 and gate.is_contiguous())
+    check(L.lib.mvlt_lamb_moments(ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(hp), ptr(tensors), nt, ptr(chunks), nc, ptr(table), n_groups, ptr(partials),
+                                  ptr(gscale_dev), ptr(gate), stream_ptr()), "mvlt_lamb_moments")
+
+
+def lamb_fold(partials, tensors, n_chunks, table, n_groups, flags, ratios, *, gate=None):
+    """LAMB launch 2: ratios[T] = ||p|| / ||u|| of every tensor that trains (1 where its weight decay is 0 unless LAMB_ALWAYS_ADAPT, and where a norm is 0;
+    min(., 1) under LAMB_TRUST_CLIP) from the partials of `lamb_moments`, summed in a fixed order; frozen tensors keep what ratios held"""
+    nt = tensors.numel() // LAMB_ROW
+    for t in (partials, table, ratios):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert tensors.dtype == torch.int64 and tensors.is_contiguous() and partials.numel() >= 2 * n_chunks and ratios.numel() >= nt and table.numel() >= 2 * n_groups
+    assert gate is None or (gate.dtype == torch.float32 and gate.numel() >= 4 and gate.is_contiguous())
+    check(L.lib.mvlt_lamb_fold(ptr(partials), n_chunks, ptr(tensors), nt, ptr(table), n_groups, int(flags), ptr(ratios), ptr(gate), stream_ptr()), "mvlt_lamb_fold")
+
+
+def lamb_apply(p, m, v, p16, n, hp, tensors, chunks, table, n_groups, ratios, *, gate=None):
+    """LAMB launch 3: p -= lr * ratios[T] * u with u recomputed from the m, v, p that `lamb_moments` left; p16 (bf16, optional) receives the new values in
+    the same pass"""
+    nt, nc = _lamb_tables_ok(tensors, chunks)
+    for t in (p, m, v, hp, table, ratios):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert min(p.numel(), m.numel(), v.numel()) >= n and hp.numel() >= 8 and table.numel() >= 2 * n_groups and ratios.numel() >= nt
+    assert p16 is None or (p16.dtype == torch.bfloat16 and p16.is_contiguous() and p16.numel() >= n)
+    assert gate is None or (gate.dtype == torch.float32 and gate.numel() >= 4 and gate.is_contiguous())
+    check(L.lib.mvlt_lamb_apply(ptr(p), ptr(m), ptr(v), ptr(p16), n, ptr(hp), ptr(tensors), nt, ptr(chunks), nc, ptr(table), n_groups, ptr(ratios), ptr(gate),
+                                stream_ptr()), "mvlt_lamb_apply")
+
+
 def ema_update(ema, p, ema16, n, decay, one_minus_decay, mask=None):
     """ema[0:n] = ema * decay + p * one_minus_decay, the two products and the sum each rounded to fp32 on its own (timm's ModelEma formula in torch's
     bits); ema16 (bf16, optional) receives the bf16 of the new values in the same pass; mask (uint8, optional): elements whose byte is ADAMW_FROZEN are

@@ -15,6 +15,9 @@ Frozen parameters (requires_grad=False) are left alone, as torch.optim.AdamW lea
 parameter of the model, and the per-element mask of the kernel carries a third value for the elements of frozen ones (neither they nor their
 moments nor their bf16 copies are written).  The mask follows requires_grad from step to step, so un-freezing needs no new optimizer.
 
+FusedLamb (docs/lamb.md): the same store, groups, masks, ring and checkpoints, stepped with LAMB -- AdamW's moments, then every tensor's update scaled by its
+own trust ratio ||p|| / ||update|| -- in three launches (include/mvlt_hip_lamb.h).
+
 skip_nonfinite=True (docs/nonfinite_guard.md): with engine.BF16Scaler(skip_nonfinite=True) in front, a step whose gradients hold Inf / NaN changes nothing
 -- the decision is taken on the device (FlatStore.gate_grads) and obeyed by the kernel, the host never reads it.  One difference from GradScaler follows:
 `_step`, the host count behind the bias corrections, counts ATTEMPTED steps, so after a skip the corrections are those of t + 1.
@@ -219,6 +222,16 @@ class FusedAdamW(torch.optim.Optimizer):
             self._hp.copy_(self._hp_pin[k], non_blocking=True)
             ev = self._hp_ev[k] = self._hp_ev[k] or torch.cuda.Event()
             ev.record()
+        self._launch(S, uniform, clip, gate)
+        # W^T / permuted conv operand copies are refreshed by the next forward; the plain bf16 copy S.C is already current,
+        # which holds as long as nothing else writes the parameters before that forward (FlatStore.versions() notices)
+        S.force_dirty = True
+        S._c_fresh_version = S.versions() if S.C is not None else None
+        return loss
+
+    def _launch(self, S, uniform, clip, gate):
+        """the launches of one step, behind the hyper-parameter row that is already on its way to the device (FusedLamb replaces this part alone)"""
+        groups = self.param_groups
         for lo, hi in phased_ranges(S):
             if self._all_frozen(lo, hi):         # nothing in the range steps: no launch
                 continue
@@ -232,11 +245,6 @@ class FusedAdamW(torch.optim.Optimizer):
                 continue
             ops.adamw_step(S.P[lo:hi], S.G[lo:hi], self._m[lo:hi], self._v[lo:hi], None if S.C is None else S.C[lo:hi], hi - lo, self._hp, self._wd_mask[lo:hi],
                            gscale_dev=clip)
-        # W^T / permuted conv operand copies are refreshed by the next forward; the plain bf16 copy S.C is already current,
-        # which holds as long as nothing else writes the parameters before that forward (FlatStore.versions() notices)
-        S.force_dirty = True
-        S._c_fresh_version = S.versions() if S.C is not None else None
-        return loss
 
     def zero_grad(self, set_to_none=True):
         super().zero_grad(set_to_none=set_to_none)
@@ -293,6 +301,93 @@ class FusedAdamW(torch.optim.Optimizer):
                 else:
                     self._m = self._v = None
                     self._pending = (fused["m"].detach().clone(), fused["v"].detach().clone())
+
+
+LAMB_MAX_CHUNKS = 64 * 256        # chunks of one tensor (268 M elements): 64 sequential additions per lane of the fold, which keeps the reduction depth at 99 (docs/lamb.md)
+
+
+def lamb_tables(layout, n, n_groups):
+    """The two tables that describe a flat buffer of n elements to the LAMB launches (include/mvlt_hip_lamb.h), as HOST tensors.
+    layout: [(offset, length, group, frozen)] per tensor, ascending.  Returns (tensors int64 [T, ops.LAMB_ROW] = {offset, length, group, frozen,
+    first_chunk, n_chunks}, chunks int32 [C, 2] = {tensor, index of the chunk in it}): a tensor is cut into ops.LAMB_CHUNK-element chunks counted from ITS
+    first element, so how a tensor is summed does not depend on where it stands or on what stands next to it; a short tensor is one short chunk, an
+    empty one none.  Checked by mvlt_lamb_check_tables before they are returned."""
+    rows, first = [], 0
+    for off, length, group, frozen in layout:
+        cnt = (length + ops.LAMB_CHUNK - 1) // ops.LAMB_CHUNK
+        if cnt > LAMB_MAX_CHUNKS:
+            raise ValueError(f"FusedLamb: a tensor of {length} elements is {cnt} chunks, more than the {LAMB_MAX_CHUNKS} the fold's error bound is stated for")
+        rows.append([off, length, group, 1 if frozen else 0, first, cnt])
+        first += cnt
+    tensors = torch.tensor(rows, dtype=torch.int64).reshape(len(rows), ops.LAMB_ROW)
+    counts = tensors[:, 5]
+    owner = torch.repeat_interleave(torch.arange(len(rows)), counts)
+    index = torch.arange(first) - tensors[owner, 4]
+    chunks = torch.stack([owner, index], 1).to(torch.int32).contiguous()
+    ops.lamb_check_tables(tensors, chunks, n, n_groups)
+    return tensors, chunks
+
+
+class FusedLamb(FusedAdamW):
+    """LAMB over the flat store (docs/lamb.md) -- what the reference's `--opt fusedlamb` asks apex for through timm.optim.create_optimizer (main_vl.py:308),
+    for the large-batch regime its linear lr scaling leads to.  AdamW's moments, then every tensor's update is scaled by its own trust ratio:
+
+        g = G * gs;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;  u = (m / bc1) / (sqrt(v / bc2) + eps) + wd p
+        r = ||p|| / ||u||  if (wd != 0 or always_adapt) and ||p|| > 0 and ||u|| > 0 else 1;  trust_clip: r = min(r, 1);  p = p - lr r u
+
+    with lr / wd of the tensor's group and both norms over the tensor's own elements.  Three launches per step (moments + partial norms per chunk, one fold
+    per tensor, apply + bf16 copy), no atomics and no host read: two runs from the same state give the same bits.  eps defaults to apex's 1e-6.  apex's own
+    max_grad_norm is not re-implemented: clipping is BF16Scaler(...)(loss, opt, clip_grad=...), whose coefficient rides in gs as it does for FusedAdamW.
+
+    Everything else is FusedAdamW's: param_groups / layer_decay_groups, frozen parameters (left alone, their NaNs reach no neighbour's norm), skip_nonfinite
+    (all three launches obey the gate), the pinned hyper-parameter ring, state_dict / load_state_dict, FusedModelEma behind it.  One difference: a trust
+    ratio needs the whole tensor, so `step` WAITS for every gradient collective the data-parallel wrapper handed over and steps the single whole range --
+    the overlap of the first AdamW launch with the tail of the all-reduce (`phased_ranges`) is given up.
+
+    `trust_ratios()`: {parameter name: 0-dim device view} of the ratios the last applied step used (1 before the first step, and for frozen tensors what
+    they last trained with); reading a value is a host read, for logging only."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, always_adapt=False, trust_clip=False, skip_nonfinite=False,
+                 param_groups=None):
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, skip_nonfinite=skip_nonfinite, param_groups=param_groups)
+        self.always_adapt, self.trust_clip = bool(always_adapt), bool(trust_clip)
+        self._lamb_key = self._tensors = self._chunks = self._partials = self._ratios = None
+        self._n_chunks = 0
+        self._any_live = False
+
+    def _ensure(self):
+        S = super()._ensure()
+        key = (S.P.data_ptr(), tuple(p.requires_grad for p in S._plist), len(self.param_groups))
+        if self._lamb_key != key:                # the store was re-materialised, or a parameter was frozen / un-frozen (as the group byte above)
+            group_ix = {id(p): i for i, g in enumerate(self.param_groups) for p in g["params"]}
+            layout = [(S.offsets[name][0], S.offsets[name][1], group_ix[id(p)], not p.requires_grad) for name, p in S.params.items()]
+            tensors, chunks = lamb_tables(layout, S.total, len(self.param_groups))
+            dev = S.P.device
+            same = self._ratios is not None and self._ratios.device == dev and self._ratios.numel() == len(layout)
+            self._tensors, self._chunks, self._n_chunks = tensors.to(dev), chunks.to(dev), chunks.shape[0]
+            self._partials = torch.zeros(max(self._n_chunks, 1), 2, device=dev)
+            if not same:
+                self._ratios = torch.ones(len(layout), device=dev)
+            self._any_live = any(not fz and n > 0 for _, n, _, fz in layout)
+            self._lamb_key = key
+        return S
+
+    def _launch(self, S, uniform, clip, gate):
+        S.wait_grads()                           # every collective: a trust ratio is a norm over whole tensors (no phased ranges)
+        if not self._any_live:                   # nothing steps: no launch
+            return
+        k = len(self.param_groups)
+        table = self._hp[8:]
+        flags = (ops.LAMB_ALWAYS_ADAPT if self.always_adapt else 0) | (ops.LAMB_TRUST_CLIP if self.trust_clip else 0)
+        ops.lamb_moments(S.P, S.G, self._m, self._v, S.total, self._hp, self._tensors, self._chunks, table, k, self._partials, gscale_dev=clip, gate=gate)
+        ops.lamb_fold(self._partials, self._tensors, self._n_chunks, table, k, flags, self._ratios, gate=gate)
+        ops.lamb_apply(S.P, self._m, self._v, S.C, S.total, self._hp, self._tensors, self._chunks, table, k, self._ratios, gate=gate)
+
+    def trust_ratios(self):
+        """{parameter name: 0-dim view of its trust ratio on the device}, in the store's order; empty before the first step"""
+        if self._ratios is None:
+            return {}
+        return {name: self._ratios[i] for i, name in enumerate(self.model.store.params)}
 
 
 _STAGE_NAME = re.compile(r"([A-Za-z_]+?)_?(\d+)")
