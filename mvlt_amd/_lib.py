@@ -1,4 +1,4 @@
-"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h, include/mvlt_hip_ema.h, include/mvlt_hip_plan.h, include/mvlt_hip_opt.h and include/mvlt_hip_lamb.h).
+"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h, include/mvlt_hip_ema.h, include/mvlt_hip_plan.h, include/mvlt_hip_opt.h, include/mvlt_hip_lamb.h and include/mvlt_hip_loss.h).
 
 The product path has NO fallback: importing this module without the built library, or calling an op without a
 GPU, raises.  torch is used only for device memory and streams.
@@ -307,6 +307,23 @@ for _name, (_res, _args) in LAMB_PROTOTYPES.items():
 LAMB_VERSION = 1         # include/mvlt_hip_lamb.h MVLT_LAMB_VERSION this binding was written against
 if lib.mvlt_lamb_version() != LAMB_VERSION:
     raise ImportError(f"LAMB entry points mismatch: {LIB_PATH} is version {lib.mvlt_lamb_version()}, the binding is version {LAMB_VERSION} (stale build? run python -m mvlt_amd.build)")
+
+# The entry points of include/mvlt_hip_loss.h (cross entropy with label smoothing and class weights, docs/loss_options.md): a table of their own, bound and
+# version-checked like the one above (tests/test_loss_cpu.py compares it with that header).
+LOSS_PROTOTYPES = {
+    "mvlt_loss_version": (_i, []),
+    "mvlt_ce_smooth_fwd": (_i, [_vp, _vp, _l, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvlt_ce_smooth_bwd": (_i, [_vp, _vp, _l, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+}
+for _name, (_res, _args) in LOSS_PROTOTYPES.items():
+    if not hasattr(lib, _name):
+        raise ImportError(f"{LIB_PATH} does not export {_name} (include/mvlt_hip_loss.h): stale build? run python -m mvlt_amd.build")
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
+LOSS_VERSION = 1         # include/mvlt_hip_loss.h MVLT_LOSS_VERSION this binding was written against
+if lib.mvlt_loss_version() != LOSS_VERSION:
+    raise ImportError(f"loss entry points mismatch: {LIB_PATH} is version {lib.mvlt_loss_version()}, the binding is version {LOSS_VERSION} (stale build? run python -m mvlt_amd.build)")
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 

@@ -80,15 +80,59 @@ class _CrossEntropyFn(torch.autograd.Function):
         return dl, None, None
 
 
-def cross_entropy(logits, labels, ignore_index=-100):
-    """F.cross_entropy(logits, labels, ignore_index=...) for 2-D logits.  Device tensors ALWAYS take the HIP row kernels (cast to fp32 / int64 first if the
-    caller hands something else; anything that is not a 2-D matrix raises): there is no ATen fallback on the GPU.  CPU tensors -- which the model cannot
-    produce; they reach this function only when tests/test_host_cpu.py checks the loss composition against the oracle -- take F.cross_entropy."""
+class _SmoothCrossEntropyFn(torch.autograd.Function):
+    """CrossEntropyLoss(mean, weight=..., label_smoothing=...) over the rows of a small fp32 logits matrix on the kernels of csrc/loss.hip (docs/loss_options.md):
+    the row pass and the fixed-order finish forward, one launch backward.  The accumulators are stored, not added to: no zeroed scratch."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, label_smoothing, weight):
+        from . import ops
+        rows, V = logits.shape
+        lse, smooth = torch.empty(rows, device=logits.device, dtype=torch.float32), torch.empty(rows, device=logits.device, dtype=torch.float32)
+        acc = torch.empty(3, device=logits.device, dtype=torch.float32)          # [numerator, den, W]
+        ops.ce_smooth_fwd(logits, labels, lse, smooth, acc, rows, V, V, ignore_index=ignore_index, label_smoothing=label_smoothing, weight=weight)
+        ctx.save_for_backward(logits, labels, lse, acc)
+        ctx.opts = (ignore_index, label_smoothing, weight)
+        return acc[0] / acc[1]                                                   # den == 0 (every row ignored): NaN, like torch
+
+    @staticmethod
+    def backward(ctx, gout):
+        from . import ops
+        logits, labels, lse, acc = ctx.saved_tensors
+        ignore_index, label_smoothing, weight = ctx.opts
+        rows, V = logits.shape
+        dl = torch.empty_like(logits)
+        ops.ce_smooth_bwd(logits, labels, lse, gout.reshape(1).float().contiguous(), acc, dl, rows, V, V, V, ignore_index=ignore_index,
+                          label_smoothing=label_smoothing, weight=weight)
+        return dl, None, None, None, None
+
+
+def check_label_smoothing(e, what="label_smoothing"):
+    e = float(e)
+    if not 0.0 <= e < 1.0:
+        raise MVLTError(f"{what} must be in [0, 1), got {e}")
+    return e
+
+
+def cross_entropy(logits, labels, ignore_index=-100, label_smoothing=0.0, weight=None):
+    """F.cross_entropy(logits, labels, weight=..., ignore_index=..., label_smoothing=...) for 2-D logits.  Device tensors ALWAYS take HIP row kernels (cast to
+    fp32 / int64 first if the caller hands something else; anything that is not a 2-D matrix raises): there is no ATen fallback on the GPU.  With
+    label_smoothing == 0 and weight None these are the plain kernels the MLM head uses, otherwise the ones of csrc/loss.hip (docs/loss_options.md); weight must
+    then be a device fp32 vector with one entry per class.  CPU tensors -- which the model cannot produce; they reach this function only when
+    tests/test_host_cpu.py checks the loss composition against the oracle -- take F.cross_entropy with the same arguments."""
     if not logits.is_cuda:
-        return F.cross_entropy(logits, labels, ignore_index=ignore_index)
+        return F.cross_entropy(logits, labels, weight=weight, ignore_index=ignore_index, label_smoothing=label_smoothing)
     if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
         raise MVLTError(f"cross_entropy: need (rows, classes) logits and (rows,) labels, got {tuple(logits.shape)} / {tuple(labels.shape)}")
-    return _CrossEntropyFn.apply(logits.float().contiguous(), labels.long().contiguous(), ignore_index)
+    label_smoothing = check_label_smoothing(label_smoothing, "cross_entropy: label_smoothing")
+    if label_smoothing == 0.0 and weight is None:
+        return _CrossEntropyFn.apply(logits.float().contiguous(), labels.long().contiguous(), ignore_index)
+    if weight is not None and not (torch.is_tensor(weight) and weight.is_cuda and weight.device == logits.device and weight.dtype == torch.float32
+                                   and weight.dim() == 1 and weight.shape[0] == logits.shape[1]):
+        raise MVLTError(f"cross_entropy: weight must be an fp32 vector of {logits.shape[1]} entries on {logits.device}, got "
+                        + (f"{weight.dtype} {tuple(weight.shape)} on {weight.device}" if torch.is_tensor(weight) else type(weight).__name__))
+    return _SmoothCrossEntropyFn.apply(logits.float().contiguous(), labels.long().contiguous(), ignore_index, label_smoothing,
+                                       None if weight is None else weight.contiguous())
 
 
 def smooth_l1(pred, target):
@@ -139,8 +183,25 @@ def _compose_hip(losses):
     return total, {k: packed[1 + i] for i, k in enumerate(LOSS_KEYS[1:])}
 
 
-def compute_losses(outputs, images, mlm_labels, itm_labels, sup_cls_labels, sub_cls_labels):
-    """Loss composition of reference engine_grid_masking.py:81-102.  Returns (total, dict of the five parts)."""
+def _ce_options(options, head, dev):
+    """keyword arguments of `cross_entropy` for one head ("mlm", "sup_cls", "sub_cls") under a model's loss options (pvlt.LossOptions, docs/loss_options.md);
+    none at all with the defaults, so that the call is the one it was"""
+    kw = {}
+    if options is None:
+        return kw
+    e = options.mlm_label_smoothing if head == "mlm" else options.cls_label_smoothing
+    if e:
+        kw["label_smoothing"] = e
+    w = getattr(options, head + "_weight", None)
+    if w is not None:
+        kw["weight"] = w if w.device == dev else w.to(dev)
+    return kw
+
+
+def compute_losses(outputs, images, mlm_labels, itm_labels, sup_cls_labels, sub_cls_labels, options=None):
+    """Loss composition of reference engine_grid_masking.py:81-102.  Returns (total, dict of the five parts).  options: the model's `loss_options`
+    (label smoothing / class weights of the MLM and the two CLS losses, docs/loss_options.md); None = the plain losses.  The fused MLM loss (`mlm_loss`) was
+    formed inside the model under the same options; ITM and T2I have none."""
     dev = images.device
     if images.is_cuda and outputs["mlm_logits"] is None:
         # device path: every loss is one HIP reduction, the composition one more launch
@@ -150,8 +211,8 @@ def compute_losses(outputs, images, mlm_labels, itm_labels, sup_cls_labels, sub_
         if outputs["itm_logits"] is not None:
             ls["loss_itm"] = cross_entropy(outputs["itm_logits"].view(-1, 2).float(), itm_labels.view(-1))
         if outputs["sup_cls_logits"] is not None:
-            ls["loss_sup_cls"] = cross_entropy(outputs["sup_cls_logits"].view(-1, 48).float(), sup_cls_labels.view(-1))
-            ls["loss_sub_cls"] = cross_entropy(outputs["sub_cls_logits"].view(-1, 122).float(), sub_cls_labels.view(-1))
+            ls["loss_sup_cls"] = cross_entropy(outputs["sup_cls_logits"].view(-1, 48).float(), sup_cls_labels.view(-1), **_ce_options(options, "sup_cls", dev))
+            ls["loss_sub_cls"] = cross_entropy(outputs["sub_cls_logits"].view(-1, 122).float(), sub_cls_labels.view(-1), **_ce_options(options, "sub_cls", dev))
         if outputs.get("t2i_loss") is not None:
             ls["loss_t2i"] = outputs["t2i_loss"].float()
         elif outputs["t2i_logits"] is not None:
@@ -165,14 +226,15 @@ def compute_losses(outputs, images, mlm_labels, itm_labels, sup_cls_labels, sub_
         parts["loss_mlm"] = MLM_LOSS_WEIGHT * outputs["mlm_loss"]
         total = total + parts["loss_mlm"]
     elif outputs["mlm_logits"] is not None:
-        parts["loss_mlm"] = MLM_LOSS_WEIGHT * cross_entropy(outputs["mlm_logits"].reshape(-1, 30522).float(), mlm_labels.view(-1), ignore_index=-1)
+        parts["loss_mlm"] = MLM_LOSS_WEIGHT * cross_entropy(outputs["mlm_logits"].reshape(-1, 30522).float(), mlm_labels.view(-1), ignore_index=-1,
+                                                            **_ce_options(options, "mlm", dev))
         total = total + parts["loss_mlm"]
     if outputs["itm_logits"] is not None:
         parts["loss_itm"] = ITM_LOSS_WEIGHT * cross_entropy(outputs["itm_logits"].view(-1, 2).float(), itm_labels.view(-1))
         total = total + parts["loss_itm"]
     if outputs["sup_cls_logits"] is not None:
-        parts["loss_sup_cls"] = cross_entropy(outputs["sup_cls_logits"].view(-1, 48).float(), sup_cls_labels.view(-1))
-        parts["loss_sub_cls"] = cross_entropy(outputs["sub_cls_logits"].view(-1, 122).float(), sub_cls_labels.view(-1))
+        parts["loss_sup_cls"] = cross_entropy(outputs["sup_cls_logits"].view(-1, 48).float(), sup_cls_labels.view(-1), **_ce_options(options, "sup_cls", dev))
+        parts["loss_sub_cls"] = cross_entropy(outputs["sub_cls_logits"].view(-1, 122).float(), sub_cls_labels.view(-1), **_ce_options(options, "sub_cls", dev))
         total = total + parts["loss_sup_cls"] + parts["loss_sub_cls"]
     if outputs["t2i_logits"] is not None:
         parts["loss_t2i"] = T2I_LOSS_WEIGHT * smooth_l1(outputs["t2i_logits"].float(), images)
@@ -191,7 +253,8 @@ def train_step(model, batch, idx, t2i_on, fused=True):
                         mlm_count=batch.get("mlm_count"), t2i_target=images if core.loss_type.get("t2i") else None)
     else:
         outputs = model(inp, batch["input_ids"])
-    return compute_losses(outputs, images, batch["mlm_labels"], batch["itm_labels"], batch["sup_cls_labels"], batch["sub_cls_labels"])
+    return compute_losses(outputs, images, batch["mlm_labels"], batch["itm_labels"], batch["sup_cls_labels"], batch["sub_cls_labels"],
+                          options=getattr(core, "loss_options", None))
 
 
 LOSS_KEYS = ("total_loss", "loss_mlm", "loss_itm", "loss_sup_cls", "loss_sub_cls", "loss_t2i")

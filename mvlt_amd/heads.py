@@ -198,7 +198,9 @@ def _mlm_decoder_bwd(model, dl, t, sv_t, e, sv_e, A, a_map, R, dA, c_map=None, a
 
 class _MLMFusedFn(torch.autograd.Function):
     """MLM head + CrossEntropyLoss(ignore_index=-1) on the selected rows only.  `positions` (int32, ascending flat
-    b*T+t indices with label != -1) is the masked-index selection; rows CE would ignore are never computed."""
+    b*T+t indices with label != -1) is the masked-index selection; rows CE would ignore are never computed.
+    With model.loss_options.mlm_label_smoothing > 0 the loss is CrossEntropyLoss(ignore_index=-1, label_smoothing=...): the (R, 30522) logits exist only
+    in here, so the smoothed loss is formed in here too."""
 
     @staticmethod
     def forward(ctx, x4, model, HW, positions, labels_sel, sink):
@@ -214,8 +216,15 @@ class _MLMFusedFn(torch.autograd.Function):
         logits = _empty((R, VOCAB_LD), torch.float32, dev)
         linear(t, P.w(WORD_TABLE), logits, bias=P.f32("mlm_head.bias"))
         lse = _empty((R,), torch.float32, dev)
-        acc = pool_zeros((2,), torch.float32, dev)                     # [loss_sum, count]; pooled scratch lives until the next forward
-        ops.cross_entropy_fwd(logits, labels_sel, lse, acc[0:1], acc[1:2], R, VOCAB, VOCAB_LD)
+        ctx.smoothing = smoothing = model.loss_options.mlm_label_smoothing      # read HERE, once: the backward applies what the forward computed
+        if smoothing:
+            # label_smoothing > 0 (set_loss_options, docs/loss_options.md): the kernels of csrc/loss.hip -- the same single pass over the logits, which also
+            # leaves each row's smoothing term; acc = [numerator, den, W], stored by the finish launch (no zeroed scratch)
+            acc = _empty((3,), torch.float32, dev)
+            ops.ce_smooth_fwd(logits, labels_sel, lse, _empty((R,), torch.float32, dev), acc, R, VOCAB, VOCAB_LD, label_smoothing=smoothing)
+        else:
+            acc = pool_zeros((2,), torch.float32, dev)                 # [loss_sum, count]; pooled scratch lives until the next forward
+            ops.cross_entropy_fwd(logits, labels_sel, lse, acc[0:1], acc[1:2], R, VOCAB, VOCAB_LD)
         ctx.pack = (model, HW, x4.shape, rows, e, sv_e, t, sv_t, logits, lse, acc, positions, labels_sel, tmap, sink)
         ctx.unit = plan_unit(model, "mlm_head")
         return acc[0] / acc[1]          # mean over selected rows (NaN when none, like torch)
@@ -229,7 +238,10 @@ class _MLMFusedFn(torch.autograd.Function):
         R = positions.numel()
         dl = _empty((R, VOCAB_LD), dt, dev)
         gs = gloss.reshape(1).float().contiguous()
-        ops.cross_entropy_bwd(logits, labels_sel, lse, gs, acc[1:2], dl, R, VOCAB, VOCAB_LD, VOCAB_LD)
+        if ctx.smoothing:
+            ops.ce_smooth_bwd(logits, labels_sel, lse, gs, acc, dl, R, VOCAB, VOCAB_LD, VOCAB_LD, label_smoothing=ctx.smoothing)
+        else:
+            ops.cross_entropy_bwd(logits, labels_sel, lse, gs, acc[1:2], dl, R, VOCAB, VOCAB_LD, VOCAB_LD)
         u = ctx.unit
         drows = _empty((R, C), dt, dev) if u.dgrad else None
         _mlm_decoder_bwd(model, dl, t, sv_t, e, sv_e, rows, None, R, drows, c_map=None, unit=u)

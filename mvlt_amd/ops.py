@@ -290,6 +290,35 @@ def cross_entropy_bwd(logits, labels, lse, gscale, count, dlogits, rows, V, ld, 
                                        DT[logits.dtype], DT[dlogits.dtype], stream_ptr()), "mvlt_cross_entropy_bwd")
 
 
+def _ce_smooth_ok(logits, labels, weight, rows, V, ld, label_smoothing):
+    assert logits.dtype in DT and logits.is_contiguous() and labels.dtype == torch.int64 and labels.is_contiguous()       # (a dtype but fp32: the entry point refuses it)
+    assert labels.numel() >= rows and (rows <= 0 or logits.numel() >= (rows - 1) * ld + V)
+    assert weight is None or (weight.dtype == torch.float32 and weight.is_contiguous() and weight.numel() >= V)
+    return float(label_smoothing)
+
+
+def ce_smooth_fwd(logits, labels, lse, smooth, acc, rows, V, ld, *, ignore_index=-1, label_smoothing=0.0, weight=None):
+    """F.cross_entropy(logits, labels, weight=weight, ignore_index=..., label_smoothing=...) over the rows of an fp32 matrix (include/mvlt_hip_loss.h): lse[r],
+    smooth[r] = W lse_r - sum_c w_c x[r, c] (written for label_smoothing > 0 only) and acc = [numerator, den, W] by plain stores -- the mean is acc[0] / acc[1].
+    weight: fp32 [V] or None."""
+    e = _ce_smooth_ok(logits, labels, weight, rows, V, ld, label_smoothing)
+    for t, n in ((lse, rows), (smooth, rows), (acc, 3)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n
+    check(L.lib.mvlt_ce_smooth_fwd(ptr(logits), ptr(labels), ignore_index, e, ptr(weight), ptr(lse), ptr(smooth), ptr(acc), rows, V, ld, DT[logits.dtype],
+                                   stream_ptr()), "mvlt_ce_smooth_fwd")
+
+
+def ce_smooth_bwd(logits, labels, lse, gscale, acc, dlogits, rows, V, ld, ldd, *, ignore_index=-1, label_smoothing=0.0, weight=None):
+    """the gradient of `ce_smooth_fwd`'s mean times the device scalar gscale, from the lse and acc it left; dlogits fp32 or bf16 [rows, ldd], its padding
+    columns [V, ldd) zeroed.  1 / den is taken as 0 when den is not positive (every row ignored); it is never clamped to 1."""
+    e = _ce_smooth_ok(logits, labels, weight, rows, V, ld, label_smoothing)
+    for t, n in ((lse, rows), (gscale, 1), (acc, 3)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n
+    assert dlogits.dtype in DT and dlogits.is_contiguous() and (rows <= 0 or dlogits.numel() >= rows * ldd)
+    check(L.lib.mvlt_ce_smooth_bwd(ptr(logits), ptr(labels), ignore_index, e, ptr(weight), ptr(lse), ptr(gscale), ptr(acc), ptr(dlogits), rows, V, ld, ldd,
+                                   DT[logits.dtype], DT[dlogits.dtype], stream_ptr()), "mvlt_ce_smooth_bwd")
+
+
 ADAMW_FROZEN = 2          # decay_mask byte of a frozen element (MVLT_ADAMW_FROZEN in include/mvlt_hip.h); 0 = step, 1 = step with weight decay
 
 

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import patchmap, rowmap
+from ._lib import MVLTError, patchmap, rowmap
 from .params import FlatStore, Holder, affine, conv_default_init_, linear, trunc_normal_
 from .plan import stage_grids
 
@@ -122,6 +122,19 @@ class _ITGHead(nn.Module):
         self.score = nn.Sequential(nn.Conv2d(3 * ch, 3, 1))
 
 
+class LossOptions:
+    """What `PyramidVisionLanguageTransformer.set_loss_options` keeps (docs/loss_options.md): the label smoothing of the MLM loss and of the two CLS losses,
+    and the class weights of the latter as fp32 tensors (None = unweighted).  The defaults are the plain losses."""
+    __slots__ = ("mlm_label_smoothing", "cls_label_smoothing", "sup_cls_weight", "sub_cls_weight")
+
+    def __init__(self):
+        self.mlm_label_smoothing, self.cls_label_smoothing, self.sup_cls_weight, self.sub_cls_weight = 0.0, 0.0, None, None
+
+    @property
+    def active(self):
+        return bool(self.mlm_label_smoothing or self.cls_label_smoothing or self.sup_cls_weight is not None or self.sub_cls_weight is not None)
+
+
 # =============================================================================================== the model
 class PyramidVisionLanguageTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dims=(64, 128, 256, 512),
@@ -185,6 +198,7 @@ class PyramidVisionLanguageTransformer(nn.Module):
         self._anchor = None
         self._transposed, self._conv_perm = self._operand_lists()
         self._conv3 = [n for n, p in self.named_parameters() if n.startswith("t2i_head.") and p.dim() == 4 and p.shape[-1] == 3]
+        self.loss_options = LossOptions()       # set_loss_options: everything off
         self.injected_masks = None      # tests: {'bert': (B,T,768) keep, 'droppath': [...], 'droppath2': [...]}
 
     # ------------------------------------------------------------------ init / state
@@ -237,6 +251,11 @@ class PyramidVisionLanguageTransformer(nn.Module):
         out = super()._apply(fn, *a, **k)
         if hasattr(self, "_store"):
             self._store.P = None                            # parameter storage was replaced: rebuild lazily
+        opts = getattr(self, "loss_options", None)
+        if opts is not None:                                # the class weights follow the parameters (.cuda(), .to(device)), in fp32 whatever the cast
+            for k in ("sup_cls_weight", "sub_cls_weight"):
+                if getattr(opts, k) is not None:
+                    setattr(opts, k, fn(getattr(opts, k)).float())
         return out
 
     @property
@@ -250,6 +269,36 @@ class PyramidVisionLanguageTransformer(nn.Module):
             self.compute_dtype = dtype
             self._store.compute_dtype = dtype
             self._store.P = None
+
+    def set_loss_options(self, mlm_label_smoothing=0.0, cls_label_smoothing=0.0, sup_cls_weight=None, sub_cls_weight=None):
+        """Label smoothing of the MLM loss and of the two CLS losses, and a weight per class for the 48 super- and the 122 sub-categories: the
+        `label_smoothing=` / `weight=` keywords of the reference's CrossEntropyLoss calls (engine_grid_masking.py:84,94,95), computed by the kernels of
+        csrc/loss.hip (docs/loss_options.md).  Every call states ALL four: calling it with no argument switches everything off, and a step then makes the
+        launches it made before.  ITM and T2I have no options.  The weights (anything torch.as_tensor takes, positive and finite) are kept as fp32 tensors on
+        the parameters' device; they are training settings, not state: neither parameters nor registered buffers, so state_dict, the EMA copy and the
+        data-parallel buffer broadcast never see them.  Returns the new `loss_options`."""
+        opts = LossOptions()
+        for name, e in (("mlm_label_smoothing", mlm_label_smoothing), ("cls_label_smoothing", cls_label_smoothing)):
+            e = float(e)
+            if not 0.0 <= e < 1.0:
+                raise MVLTError(f"set_loss_options: {name} must be in [0, 1), got {e}")
+            setattr(opts, name, e)
+        dev = next(self.parameters()).device
+        for name, w, n in (("sup_cls_weight", sup_cls_weight, 48), ("sub_cls_weight", sub_cls_weight, 122)):
+            if w is None:
+                continue
+            w = torch.as_tensor(w).detach().float()
+            if tuple(w.shape) != (n,):
+                raise MVLTError(f"set_loss_options: {name} must hold {n} entries, got shape {tuple(w.shape)}")
+            if not bool((torch.isfinite(w) & (w > 0)).all()):
+                raise MVLTError(f"set_loss_options: {name} must be positive and finite")
+            setattr(opts, name, w.to(dev).contiguous().clone())
+        if (opts.cls_label_smoothing or opts.sup_cls_weight is not None or opts.sub_cls_weight is not None) and not self.loss_type.get("cls"):
+            raise MVLTError("set_loss_options: this model has no CLS heads (loss_type['cls'] is off)")
+        if opts.mlm_label_smoothing and not self.loss_type.get("mlm"):
+            raise MVLTError("set_loss_options: this model has no MLM head (loss_type['mlm'] is off)")
+        self.loss_options = opts
+        return opts
 
     # ------------------------------------------------------------------ forward
     def forward(self, input_images, input_ids, mlm_labels=None, mlm_positions=None, mlm_count=None, t2i_target=None):
