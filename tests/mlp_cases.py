@@ -219,6 +219,12 @@ def gemm_case(M, N, K, seed):
     in runs of 1, 2, 3: h = A W^T + bias, its activation G and, for act 2, the integer product v = A W^T against the pre-activation H = h"""
     A = sparse_pm1(M, K, 16, seed)
     W = torch.randint(-2, 3, (N, K), generator=gen(seed + 1)).double()
+    return saturated(A, W)
+
+
+def saturated(A, W):
+    """gemm_case on given float64 operands (tests/gemm_inst_cases.py hands over a GATHERED A): the bias magnitude is SAT plus the maximum of this product"""
+    N = W.shape[0]
     v = A @ W.t()
     mag = SAT + float(v.abs().max())
     n = torch.arange(N)

@@ -11,110 +11,16 @@ import ctypes as C_
 import pytest
 import torch
 
+from tests.gemm_inst_cases import (BF, F16, F32, LIM, dev, exact, gather_3x3, gather_patch, integral, ints, last_kernel, pad_cols, phys_rows, picks,     # noqa: F401
+                                    ran, sparse_pm1)          # (the helpers live beside the instantiation cases, tests/gemm_inst_cases.py; other test files import them from here)
+
 pytestmark = pytest.mark.gpu
-
-BF, F32, F16 = torch.bfloat16, torch.float32, torch.float16
-LIM = float(2 ** 24)
-
-
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a MI355X"
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
 def ops():
     from mvlt_amd import ops as _ops
     return _ops
-
-
-def last_kernel():
-    from mvlt_amd._lib import last_kernel as lk
-    return lk()
-
-
-def ran(family):
-    """the kernel launched last on this thread must be of `family`: a prefix of the demangled instantiation name.  (Instantiations over the bf16 element type come
-    back mangled where the C++ runtime's demangler does not know that type: the kernel's name and the type code are looked up in the mangled form then.)"""
-    name = last_kernel()
-    if name.startswith("_Z"):
-        base = family.split("<")[0]
-        assert f"{len(base)}{base}I" in name and "DF16b" in name and "<float" not in family, f"meant to reach {family}, the library launched {name}"
-        return
-    assert name.startswith(family), f"meant to reach {family}, the library launched {name}"
-
-
-def ints(shape, lo, hi, dtype, seed):
-    """uniform integers in [lo, hi] from a seeded CPU generator, cast to `dtype`, on the device"""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    shape = (shape,) if isinstance(shape, int) else tuple(shape)
-    return torch.randint(lo, hi + 1, shape, generator=g).to(dtype).to(dev())
-
-
-def picks(shape, values, seed):
-    """fp32 entries drawn uniformly from `values` (the DropPath factors {0, 0.5, 1, 2})"""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    shape = (shape,) if isinstance(shape, int) else tuple(shape)
-    return torch.tensor(values, dtype=F32)[torch.randint(0, len(values), shape, generator=g)].to(dev())
-
-
-def sparse_pm1(M, N, P, dtype, seed):
-    """[M, N] with +-1 exactly where n % P == m % P: every column holds at most ceil(M / P) nonzero rows and (for N >= P) every row at least one"""
-    sign = ints((M, N), 0, 1, F32, seed) * 2 - 1
-    m = torch.arange(M, device=dev())[:, None] % P
-    n = torch.arange(N, device=dev())[None, :] % P
-    return (sign * (m == n)).to(dtype)
-
-
-def integral(ref64, unit=1.0):
-    """the reference must be exact in fp32: whole multiples of `unit` (a power of two) below 2^24 units"""
-    q = ref64 / unit
-    assert torch.equal(q, q.round()) and float(q.abs().max()) < LIM, "the reference is not an integer below 2^24: the case itself is wrong"
-    return ref64
-
-
-def exact(out, ref64, what=""):
-    """fp32 out: equal to the float64 reference; bf16 / fp16 out: the reference rounded once to nearest-even"""
-    assert out.shape == ref64.shape, (out.shape, ref64.shape)
-    if out.dtype == F32:
-        got, want = out.double(), ref64
-    else:
-        got, want = out, ref64.float().to(out.dtype)
-    if torch.equal(got, want):
-        return
-    bad = (got != want).reshape(got.shape[0], -1) if got.dim() > 1 else (got != want).reshape(-1, 1)
-    g2, w2 = got.reshape(bad.shape), want.reshape(bad.shape)
-    idx = bad.nonzero()
-    first = [(int(r), int(c), float(g2[r, c]), float(w2[r, c])) for r, c in idx[:8].tolist()]
-    raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements wrong; first (row, col, got, want): {first}; rows {int(idx[:, 0].min())}..{int(idx[:, 0].max())}, "
-                         f"cols {int(idx[:, 1].min())}..{int(idx[:, 1].max())}; last kernel {last_kernel()}")
-
-
-def pad_cols(t, ld, fill=0):
-    out = torch.full((t.shape[0], ld), fill, device=t.device, dtype=t.dtype)
-    out[:, : t.shape[1]] = t
-    return out
-
-
-def phys_rows(n_batch, rows, stride, off):
-    return (torch.arange(n_batch, device=dev())[:, None] * stride + off + torch.arange(rows, device=dev())[None, :]).reshape(-1)
-
-
-def gather_patch(X, Bsz, r, h_out, w_out, tokens_in):
-    """mode-1 operand as a matrix: row (b, oi, oj), column (di*r + dj)*C + c = X[b*tokens_in + (oi*r+di)*w_in + oj*r+dj, c]"""
-    Cs, w_in = X.shape[-1], r * w_out
-    img = X.reshape(Bsz, tokens_in, Cs)[:, : h_out * r * w_in].reshape(Bsz, h_out, r, w_out, r, Cs)
-    return img.permute(0, 1, 3, 2, 4, 5).reshape(Bsz * h_out * w_out, r * r * Cs)
-
-
-def gather_3x3(X, Bsz, h, w, tokens_in):
-    """mode-2 operand as a matrix: row (b, y, x), column (dy*3 + dx)*C + c = X[b, (y+dy-1)*w + x+dx-1, c], zero outside the grid"""
-    Cs = X.shape[-1]
-    img = X.reshape(Bsz, tokens_in, Cs)[:, : h * w].reshape(Bsz, h, w, Cs)
-    pad = torch.zeros(Bsz, h + 2, w + 2, Cs, device=X.device, dtype=X.dtype)
-    pad[:, 1:-1, 1:-1] = img
-    taps = [pad[:, dy: dy + h, dx: dx + w] for dy in range(3) for dx in range(3)]
-    return torch.stack(taps, 3).reshape(Bsz * h * w, 9 * Cs)
 
 
 # ================================================================== gemm_nt
@@ -334,7 +240,14 @@ CONV3_NT = [  # h, w, Cin, Cout, variant, family (bf16), family (fp32)
     (5, 12, 16, 72, "plain", "gemm_nt_dma_kernel<128, 2, 1, 64", "gemm_nt_kernel<float, 128>"),       # not a halo shape: the generic gathered GEMM
     (5, 12, 16, 40, "acc", "gemm_nt_dma_kernel<64, 2, 2, 64", "gemm_nt_kernel<float, 64>"),
     (5, 12, 16, 192, "stats", "gemm_nt_dma_kernel<192, 2, 5, 64", "gemm_nt_kernel<float, 128>"),
+    # three 128-pixel tiles per image: the interior tile's halo rows are a neighbouring tile's real pixels (above: one tile per image, every halo row zero padding
+    # or inside the tile).  Two channel slices; two column tiles on BN 128 and on BN 192; the plain, statistics and residual epilogues
+    (24, 16, 128, 256, "plain", "conv3_nt_kernel<16, 128, 1>", "gemm_nt_kernel<float, 128>"),
+    (12, 32, 64, 384, "stats", "conv3_nt_kernel<32, 128, 5>", "gemm_nt_kernel<float, 128>"),       # (384 = 3 x 128: the 192-wide tile is for N % 128 != 0 only)
+    (12, 32, 64, 576, "stats", "conv3_nt_kernel<32, 192, 5>", "gemm_nt_kernel<float, 128>"),       # three column tiles on BN 192
+    (6, 64, 64, 128, "acc", "conv3_nt_kernel<64, 128, 2>", "gemm_nt_kernel<float, 128>"),
 ]
+CONV3_DGRAD = [(24, 16, 64, 128, "conv3_nt_kernel<16, 64, 1>"), (12, 32, 192, 64, "conv3_nt_kernel<32, 192, 1>"), (6, 64, 128, 64, "conv3_nt_kernel<64, 128, 1>")]      # h, w, Cin, Cout, family
 
 
 @pytest.mark.parametrize("dtype", [BF, F32])
@@ -386,6 +299,32 @@ def test_gemm_nt_conv3x3_gather(ops, dtype, h, w, Cin, Cout, variant, fam_bf, fa
         keep = torch.ones(Bsz * stride, dtype=torch.bool, device=dev())
         keep[sel] = False
         assert (buf[keep] == 7.0).all()
+
+
+@pytest.mark.parametrize("h,w,Cin,Cout,family", CONV3_DGRAD)
+def test_gemm_nt_conv3x3_input_gradient(ops, h, w, Cin, Cout, family):
+    """the input gradient as the MIM decoder takes it: the same 3x3 gather over dz with flipped, transposed taps, three tiles per image.  The reference does not
+    flip: dx[b, y, x, ci] = sum over (dy, dx, co) of dz[b, y - dy + 1, x - dx + 1, co] W[co, dy, dx, ci], tap by tap in float64"""
+    from mvlt_amd._lib import conv3map
+    Bsz, T = 3, 5
+    tokens, M = h * w + T, Bsz * h * w
+    dz = ints((Bsz, tokens, Cout), -3, 3, BF, 52)
+    dz[:, h * w:] = 99
+    Wk = ints((Cout, 3, 3, Cin), -3, 3, BF, 53)                                # [out][kh][kw][cin], the forward layout
+    Wf = Wk.flip(1, 2).permute(3, 1, 2, 0).reshape(Cin, 9 * Cout).contiguous()      # [cin][flipped tap][out]
+    pad = torch.zeros(Bsz, h + 2, w + 2, Cout, device=dev(), dtype=torch.float64)
+    pad[:, 1:-1, 1:-1] = dz[:, : h * w].double().reshape(Bsz, h, w, Cout)
+    ref = torch.zeros(Bsz, h, w, Cin, device=dev(), dtype=torch.float64)
+    for dy in range(3):
+        for dx in range(3):
+            ref += pad[:, 2 - dy: 2 - dy + h, 2 - dx: 2 - dx + w] @ Wk[:, dy, dx].double()
+    ref = integral(ref.reshape(M, Cin))
+    for odt in (F32, BF):
+        out = torch.full((M + 1, Cin), 7.0, device=dev(), dtype=odt)
+        ops.gemm_nt(dz, Wf, out, M, Cin, 9 * Cout, Cout, 9 * Cout, Cin, a_map=conv3map(h, w, tokens, Cout))
+        ran(family)
+        exact(out[:M], ref, f"conv3x3 input gradient {odt}")
+        assert (out[M] == 7.0).all()
 
 
 @pytest.mark.parametrize("N,K,M,odt", [(64, 72, 257, F32), (128, 200, 257, F32), (64, 72, 130, BF)])
@@ -526,7 +465,10 @@ def test_gemm_tn_patch_gather_and_taps(ops, dtype, r, h_out, w_out, Cin, Cout):
 
 
 CONV3_TN = [(4, 16, 64, 64, "conv3_wgrad_kernel<16>"), (8, 8, 64, 128, "conv3_wgrad_kernel<8>"), (2, 32, 128, 64, "conv3_wgrad_kernel<32>"), (1, 64, 64, 64, "conv3_wgrad_kernel<64>"),
-            (5, 12, 16, 72, "gemm_tn_dma_kernel<128, 128, 2, 2, false>"), (5, 12, 8, 40, "gemm_tn_dma_kernel<64, 64, 2, 4, false>")]
+            (5, 12, 16, 72, "gemm_tn_dma_kernel<128, 128, 2, 2, false>"), (5, 12, 8, 40, "gemm_tn_dma_kernel<64, 64, 2, 4, false>"),
+            # three 64-pixel k-tiles per image (the middle one's halo rows are its neighbours' pixels), two output and two channel slices: n_o n_c = 4
+            (24, 8, 128, 128, "conv3_wgrad_kernel<8>"), (12, 16, 128, 128, "conv3_wgrad_kernel<16>"), (6, 32, 128, 128, "conv3_wgrad_kernel<32>"),
+            (3, 64, 128, 128, "conv3_wgrad_kernel<64>")]
 
 
 @pytest.mark.parametrize("h,w,Cin,Cout,family", CONV3_TN)
@@ -663,7 +605,10 @@ def test_gemm_tn_partial_tiles(ops, route, M, N1, N2, family, swap):
 
 
 @pytest.mark.parametrize("swap", [False, True])
-@pytest.mark.parametrize("h,w,Bsz,Cin,Cout,family", [(32, 32, 4, 64, 64, "conv3_wgrad_kernel<32>"), (16, 16, 16, 64, 128, "conv3_wgrad_kernel<16>")])
+@pytest.mark.parametrize("h,w,Bsz,Cin,Cout,family", [(32, 32, 4, 64, 64, "conv3_wgrad_kernel<32>"), (16, 16, 16, 64, 128, "conv3_wgrad_kernel<16>"),
+                                                     # three k-tiles per image, 22 images = 66 k-tiles = 4 splits of 17: a split ends inside an image
+                                                     (24, 8, 22, 128, 128, "conv3_wgrad_kernel<8>"), (12, 16, 22, 128, 128, "conv3_wgrad_kernel<16>"),
+                                                     (6, 32, 22, 128, 128, "conv3_wgrad_kernel<32>"), (3, 64, 22, 128, 128, "conv3_wgrad_kernel<64>")])
 def test_gemm_tn_partial_tiles_conv3x3(ops, h, w, Bsz, Cin, Cout, family, swap):
     """route (c): the conv3x3 weight-gradient kernel with >= 4 m-splits.  The bound of 256 is asserted on the gathered operand."""
     from mvlt_amd._lib import conv3map
