@@ -775,6 +775,14 @@ inline int grid_for(long work, int cap = 4096) {
 // libs/pvlt.py:295-297 on the learned position embeddings): src = (dst + 0.5) * in/out - 0.5 clamped at 0, neighbours
 // floor(src) and min(floor(src)+1, in-1).  ADJ = false: out[(y,x), c] = sum of 4 weighted inputs.  ADJ = true: the adjoint --
 // `in` is the gradient w.r.t. the resized map, every element is scattered (atomics) into the gradient of the source map `out`.
+// source coordinate of target index o: max(s * (o + 0.5) - 0.5, 0) in exactly these float32 roundings.  The product is rounded BEFORE the subtraction (the empty
+// asm keeps the compiler from contracting the two into one fma): a contracted coordinate differs by an ulp of the coordinate, which the difference of two
+// neighbouring pixels turns into an error far above the roundings of the interpolation itself -- and a host reference could not say which of the two it gets.
+__device__ __forceinline__ float resize_src_coord(float s, int o) {
+  float p = s * ((float)o + 0.5f);
+  asm volatile("" : "+v"(p));
+  return fmaxf(p - 0.5f, 0.f);
+}
 template <bool ADJ>
 __global__ __launch_bounds__(NT) void resize_tokens_kernel(const float* in, int ld_in, float* out, int ld_out, int Hin, int Win, int Hout, int Wout,
                                                            int C, float sh, float sw) {
@@ -783,10 +791,12 @@ __global__ __launch_bounds__(NT) void resize_tokens_kernel(const float* in, int 
     const int c = (int)(i % C);
     const int px = (int)(i / C);
     const int y = px / Wout, x = px - y * Wout;
-    const float fy = fmaxf(sh * ((float)y + 0.5f) - 0.5f, 0.f), fx = fmaxf(sw * ((float)x + 0.5f) - 0.5f, 0.f);
+    const float fy = resize_src_coord(sh, y), fx = resize_src_coord(sw, x);
     const int y0 = (int)fy, x0 = (int)fx;
     const int y1 = y0 + (y0 < Hin - 1 ? 1 : 0), x1 = x0 + (x0 < Win - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    // a clamped neighbour IS the pixel itself: its weight is 0 and the pixel's 1, exactly (a 1-pixel source axis and the last row / column are copied, not
+    // recombined from two rounded halves)
+    const float ly = y0 < Hin - 1 ? fy - (float)y0 : 0.f, lx = x0 < Win - 1 ? fx - (float)x0 : 0.f;
     const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
     if constexpr (!ADJ) {
       out[(long)px * ld_out + c] = w00 * in[(long)(y0 * Win + x0) * ld_in + c] + w01 * in[(long)(y0 * Win + x1) * ld_in + c] +
@@ -816,10 +826,12 @@ __global__ __launch_bounds__(NT) void resize_tokens_multi_kernel(ResizeMulti a) 
     const int c = (int)(i % C);
     const int px = (int)(i / C);
     const int y = px / Wout, x = px - y * Wout;
-    const float fy = fmaxf(sh * ((float)y + 0.5f) - 0.5f, 0.f), fx = fmaxf(sw * ((float)x + 0.5f) - 0.5f, 0.f);
+    const float fy = resize_src_coord(sh, y), fx = resize_src_coord(sw, x);
     const int y0 = (int)fy, x0 = (int)fx;
     const int y1 = y0 + (y0 < Hin - 1 ? 1 : 0), x1 = x0 + (x0 < Win - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    // a clamped neighbour IS the pixel itself: its weight is 0 and the pixel's 1, exactly (a 1-pixel source axis and the last row / column are copied, not
+    // recombined from two rounded halves)
+    const float ly = y0 < Hin - 1 ? fy - (float)y0 : 0.f, lx = x0 < Win - 1 ? fx - (float)x0 : 0.f;
     const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
     if constexpr (!ADJ) {
       out[(long)px * ld_out + c] = w00 * in[(long)(y0 * Win + x0) * ld_in + c] + w01 * in[(long)(y0 * Win + x1) * ld_in + c] +
@@ -980,6 +992,7 @@ extern "C" int mvlt_gather_rows(const void* src, const int* idx, void* dst, int 
   MVLT_REQUIRE(src && idx && dst, "mvlt_gather_rows: null pointer");
   const int pc = dtype == 0 ? 8 : 4;
   MVLT_REQUIRE(C % pc == 0 && ld_src % pc == 0, "mvlt_gather_rows: C/ld must be multiples of %d", pc);
+  MVLT_REQUIRE(!src_map || src_map->mode == 0, "mvlt_gather_rows: src_map must be a mode-0 row map or NULL, got mode %d", src_map->mode);
   if (rows <= 0) return MVLT_OK;
   dim3 grid(grid_for((long)rows * (C / pc))), block(NT);
   RowMap m = host_rowmap(src_map);
@@ -992,6 +1005,7 @@ extern "C" int mvlt_scatter_rows(const void* src, const int* idx, void* dst, int
   MVLT_REQUIRE(src && idx && dst, "mvlt_scatter_rows: null pointer");
   const int pc = dtype == 0 ? 8 : 4;
   MVLT_REQUIRE(C % pc == 0 && ld_dst % pc == 0, "mvlt_scatter_rows: C/ld must be multiples of %d", pc);
+  MVLT_REQUIRE(!dst_map || dst_map->mode == 0, "mvlt_scatter_rows: dst_map must be a mode-0 row map or NULL, got mode %d", dst_map->mode);
   if (rows <= 0) return MVLT_OK;
   dim3 grid(grid_for((long)rows * (C / pc))), block(NT);
   RowMap m = host_rowmap(dst_map);

@@ -54,6 +54,45 @@ def conv_default_init_(w, b):
         nn.init.uniform_(b, -bound, bound)
 
 
+def prep_blocks(d):
+    """workgroups of one mvlt_prep_desc: 64 x 64 tiles of a transpose (kind 0 / 2), 256 elements of a gather (kind 1)"""
+    if d.kind == 1:
+        return (d.d0 * d.d1 * d.d2 + 255) // 256
+    return ((d.R + 63) // 64) * ((d.C + 63) // 64)
+
+
+def pack_prep_table(descs, dtype, device):
+    """The device tables of one mvlt_weight_prep launch over `descs` (a list of _lib.PrepDesc) whose destinations are of `dtype`:
+    -> (descriptor bytes, blk_start int32 [ndesc + 1], ndesc, total_blocks, blk_desc int32 [total_blocks]) as ops.weight_prep takes them.
+    The C entry point cannot read a device table, so what it could not check is checked here: a kind-2 descriptor (bf16 source, 16-byte accesses)
+    exists only in the bf16 instantiation of the kernel -- in an fp32 launch it compiles to nothing and would leave its destination unwritten."""
+    import ctypes
+    from ._lib import MVLTError, PrepDesc
+    blocks = []
+    for i, d in enumerate(descs):
+        if d.kind not in (0, 1, 2):
+            raise MVLTError(f"weight_prep descriptor {i}: kind {d.kind} is not 0 (transpose), 1 (gather) or 2 (bf16 transpose)")
+        if d.kind == 2 and dtype != torch.bfloat16:
+            raise MVLTError(f"weight_prep descriptor {i}: kind 2 (transpose of a bf16 source) needs a bf16 destination, the table is {dtype}")
+        if d.kind == 2 and (d.C % 8 or d.ld_out % 8):
+            raise MVLTError(f"weight_prep descriptor {i}: kind 2 needs C and ld_out in multiples of 8, got C {d.C}, ld_out {d.ld_out}")
+        if d.kind != 1 and d.ld_out < d.R:
+            raise MVLTError(f"weight_prep descriptor {i}: ld_out {d.ld_out} < R {d.R}")
+        b = prep_blocks(d)
+        if b < 1:
+            raise MVLTError(f"weight_prep descriptor {i}: empty")
+        blocks.append(b)
+    arr = (PrepDesc * len(descs))(*descs)
+    raw = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr))), dtype=torch.uint8)
+    starts = [0]
+    for b in blocks:
+        starts.append(starts[-1] + b)
+    blk = torch.tensor(starts, dtype=torch.int32, device=device)
+    # block -> descriptor (the inverse of the prefix sums): the kernel's workgroups look themselves up with two scalar loads
+    blk_desc = torch.repeat_interleave(torch.arange(len(blocks), dtype=torch.int32), torch.tensor(blocks)).to(torch.int32).to(device)
+    return raw.to(device), blk, len(descs), starts[-1], blk_desc
+
+
 class ZeroPool:
     """Per-step scratch that must start at zero (atomic accumulation targets: weight-gradient tiles, BN statistics, dK/dV,
     split-K partial sums ...).  One `zero_()` of a pooled buffer at the start of a step replaces ~50 tiny fill launches;
@@ -264,7 +303,6 @@ class FlatStore:
     def _build_prep(self, transposed, conv_perm, conv3):
         """Descriptor table of every derived weight copy (one mvlt_weight_prep launch per step refreshes them all).
         The destination tensors are allocated once here; their addresses are baked into the table."""
-        import ctypes
         from ._lib import PrepDesc
         dt, dev = self.compute_dtype, self.device
         descs, blocks = [], []
@@ -316,16 +354,8 @@ class FlatStore:
         self._prep_n = len(descs)
         if not descs:
             return
-        arr = (PrepDesc * len(descs))(*descs)
-        raw = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr))), dtype=torch.uint8)
-        self._prep_desc = raw.to(dev)
-        starts = [0]
-        for b in blocks:
-            starts.append(starts[-1] + b)
-        self._prep_blk = torch.tensor(starts, dtype=torch.int32, device=dev)
-        self._prep_blocks = starts[-1]
-        # block -> descriptor (the inverse of the prefix sums): the kernel's workgroups look themselves up with two scalar loads
-        self._prep_blk_desc = torch.repeat_interleave(torch.arange(len(blocks), dtype=torch.int32), torch.tensor(blocks)).to(torch.int32).to(dev)
+        assert blocks == [prep_blocks(d) for d in descs]
+        self._prep_desc, self._prep_blk, self._prep_n, self._prep_blocks, self._prep_blk_desc = pack_prep_table(descs, dt, dev)
 
     # ------------------------------------------------------------------ gradients
     def begin_backward(self):
