@@ -165,6 +165,10 @@ class FusedAdamW(torch.optim.Optimizer):
             # ... and next to it the byte mvlt_adamw_step_groups reads: the index of the parameter's group, 255 for frozen parameters and alignment gaps
             group_ix = {id(p): i for i, g in enumerate(self.param_groups) for p in g["params"]}
             ids_nd = {k for k, i in group_ix.items() if not key[2][i]}
+            lost = [name for name, p in S.params.items() if id(p) not in group_ix]
+            if lost:       # a Parameter (or the module holding it) was replaced after this optimizer was built: the store re-materialised around the new one
+                raise RuntimeError(f"{type(self).__name__}: parameter {lost[0]!r} of the model is in no parameter group ({len(lost)} in all) -- it was replaced "
+                                   "after the optimizer was built; build a new optimizer (or add_param_group the new parameters)")
             mask = torch.zeros(S.total, dtype=torch.uint8)
             group_of = torch.full((S.total,), ops.OPT_FROZEN, dtype=torch.uint8)
             runs = []
@@ -222,11 +226,12 @@ class FusedAdamW(torch.optim.Optimizer):
             self._hp.copy_(self._hp_pin[k], non_blocking=True)
             ev = self._hp_ev[k] = self._hp_ev[k] or torch.cuda.Event()
             ev.record()
+        c_current = S.c_is_current()             # before the launch: was the bf16 copy current for the parameters this step starts from?
         self._launch(S, uniform, clip, gate)
-        # W^T / permuted conv operand copies are refreshed by the next forward; the plain bf16 copy S.C is already current,
-        # which holds as long as nothing else writes the parameters before that forward (FlatStore.versions() notices)
-        S.force_dirty = True
-        S._c_fresh_version = S.versions() if S.C is not None else None
+        # W^T / permuted conv operand copies are refreshed by the next forward.  The plain bf16 copy S.C is declared current only when the launches
+        # left it so: frozen elements and a closed step gate keep the copy they had, which is the parameters' only if nothing wrote them since the last
+        # forward (FlatStore.c_written_by_kernel).  Afterwards it holds as long as nothing else writes the parameters (FlatStore.versions() notices)
+        S.c_written_by_kernel(c_current, wrote_all=gate is None and all(self._mask_key[1]))
         return loss
 
     def _launch(self, S, uniform, clip, gate):
@@ -487,6 +492,7 @@ class FusedModelEma:
             if src.__dict__.get(k) is not None:
                 memo[id(src.__dict__[k])] = None
         self.ema = copy.deepcopy(src, memo)
+        self.ema.__dict__.pop("_mim_fold", None)      # (copied as None when the source had one: MimStep._folded wants a dict of the copy's own, or nothing)
         slots = [k for k, v in vars(src).items() if v is S]
         if not slots:
             raise RuntimeError("FusedModelEma: the model does not hold its FlatStore as an attribute")
@@ -569,17 +575,16 @@ class FusedModelEma:
         # Is the averaged model's bf16 copy current for its parameters as they stand BEFORE this launch?  Yes when its last refresh() cast (or accepted) it at this
         # version, or when an earlier update declared it fresh at this version; no for a store that has just been materialised (C is uninitialised: refresh()
         # makes the first cast) and after set() / load_state_dict() wrote the parameters.
-        ver = E.versions()
-        c_current = E.C is not None and ver in (E._cast_version, E._c_fresh_version)
+        c_current = E.c_is_current()
         ops.ema_update(E.P, S.P, E.C, S.total, d, 1.0 - d, self._mask)
         if self._buf_n:
             ops.ema_update_buffers(self._buf_table, self._buf_n, d, 1.0 - d)
         self.updates += 1
         # as after FusedAdamW.step: the W^T / permuted conv copies (and what the MIM decoder folds out of the BatchNorm buffers) are refreshed by the averaged
         # model's next forward.  Its plain bf16 copy is declared current -- the forward then skips its cast -- only when this launch left it so: it wrote every
-        # element (no mask), or the elements the mask made it skip were current already.  Otherwise refresh() casts, as for any store.
-        E.force_dirty = True
-        E._c_fresh_version = E.versions() if E.C is not None and (self._mask is None or c_current) else None
+        # element (no mask), or the elements the mask made it skip were current already.  Otherwise refresh() casts, as for any store (one rule for
+        # the optimizers and this update: FlatStore.c_written_by_kernel).
+        E.c_written_by_kernel(c_current, wrote_all=self._mask is None)
 
     @torch.no_grad()
     def set(self, model):

@@ -168,6 +168,7 @@ class FlatStore:
         self._views = {}
         self.offsets = OrderedDict()      # name -> (offset, numel, shape)
         self.params = OrderedDict()       # name -> Parameter (unique)
+        self._module_slots, self._param_slots = [], []     # where the module tree holds them (is_current)
         self.total = 0
         self._cast_version = -1
         self.refresh_count = 0                   # bumped whenever refresh() rebuilds the derived copies
@@ -210,13 +211,26 @@ class FlatStore:
         self.total = off
         # parameters whose gradients the HIP schedule writes itself: all of them
         self.fn_params = list(self.params.items())
+        # Where the module tree holds what was indexed: every child slot (the parent's `_modules` dict, key, child) and every parameter slot (the
+        # owner's `_parameters` dict, key, Parameter, element offset) -- the tied decoder weight has two of the latter.  is_current() re-reads the
+        # slots, so a child module or a Parameter that was ASSIGNED anew, anywhere in the model, is noticed without walking the tree again.
+        self._module_slots = [(m._modules, k, c) for m in self.module.modules() for k, c in m._modules.items() if c is not None]
+        off_of = {id(p): self.offsets[name][0] for name, p in self.params.items()}
+        self._param_slots = [(m._parameters, k, p, off_of[id(p)]) for m in self.module.modules() for k, p in m._parameters.items() if p is not None]
 
     def is_current(self):
+        """Does every Parameter the module tree holds NOW live at its slice of P?  False after nn.Module.to() / .cuda() (new storage), after
+        `p.data = tensor`, and after a Parameter or a whole child module was replaced (`model.sup_cls_head = Holder(...)` for a fine-tune): the
+        caller re-materialises then.  A few hundred dict and integer reads per forward (docs/coherence.md)."""
         if self.P is None:
             return False
-        for name in (next(iter(self.params)), next(reversed(self.params))):
-            off, n, _ = self.offsets[name]
-            if self.params[name].data_ptr() != self.P.data_ptr() + 4 * off:
+        for d, k, c in self._module_slots:
+            if d.get(k) is not c:
+                return False
+        base = self.P.data_ptr()
+        for d, k, p, off in self._param_slots:
+            q = d.get(k)
+            if q is not p or q.data_ptr() != base + 4 * off:
                 return False
         return True
 
@@ -277,8 +291,33 @@ class FlatStore:
         """Write counter of the master parameters.  After materialize() every Parameter is its own view of P with its own
         version counter: load_state_dict, torch.optim steps, EMA copies and p.mul_() bump the Parameter's, collectives and
         flat-buffer ops on P bump P's -- so both are read (a few hundred integer attribute reads per forward).  Writers that
-        go through the C ABI (FusedAdamW) bump neither and set force_dirty."""
+        go through the C ABI (FusedAdamW) bump neither and set force_dirty.
+        One writer is invisible here: `p.data` is a tensor with a version counter of its own, so `p.data.mul_(2)` (or any in-place op on
+        `p.data` / `p.detach()`) bumps nothing this sum reads.  Whoever writes that way calls invalidate() afterwards (docs/coherence.md)."""
         return self.P._version + sum(p._version for p in self._plist)
+
+    def invalidate(self):
+        """The masters were written in a way versions() cannot see (`p.data.<op>_()`, a kernel through raw pointers): the next refresh() casts the
+        bf16 copy again and rebuilds every derived copy, whatever an optimizer or an EMA update declared fresh before."""
+        self.force_dirty = True
+        self._c_fresh_version = None
+        self._cast_version = -1
+
+    def c_is_current(self):
+        """Is the bf16 copy C current for the masters as they stand now?  Yes when the last refresh() cast (or accepted) it at this version, or
+        when a fused writer declared it fresh at this version; no for a store that has just been materialised (C is uninitialised) and after
+        anything wrote the parameters since.  The fused writers ask this BEFORE their launch (c_written_by_kernel)."""
+        return self.C is not None and self.versions() in (self._cast_version, self._c_fresh_version)
+
+    def c_written_by_kernel(self, was_current, wrote_all):
+        """A kernel has just written P through the C ABI together with the bf16 copy of every element it wrote (FusedAdamW / FusedLamb.step,
+        FusedModelEma.update).  The W^T / permuted conv copies are refreshed by the next forward in any case; C itself is declared current -- that
+        forward then skips its cast -- only when the launch left it so: it wrote every element (`wrote_all`: nothing frozen, no step gate that may
+        have closed), or the elements it left alone were current already (`was_current` = c_is_current() before the launch).  Otherwise a write
+        to the parameters between the last forward and the step (load_state_dict, p.mul_(), a broadcast) would stay out of C for the elements
+        the kernel skipped, and refresh() casts, as for any store."""
+        self.force_dirty = True
+        self._c_fresh_version = self.versions() if self.C is not None and (wrote_all or was_current) else None
 
     def refresh(self, transposed, conv_perm, conv3=()):
         """Bring compute-dtype copies up to date with the fp32 masters.

@@ -396,6 +396,7 @@ def test_weight_prep_copies_equal_their_definitions_on_both_lookup_paths():
     definition from the fp32 master (reference libs/pvlt.py:104,168, libs/vl_heads.py:107-165 keep one layout and let cuDNN / cuBLAS permute), with the host's
     block -> descriptor table and with the per-workgroup search the kernel falls back to without it."""
     from mvlt_amd import pvlt, ops
+    from tests.coherence_cases import f_copy, k_copy, kt_copy, t_copy       # the four layout definitions (shared with tests/test_coherence_gpu.py)
     dev = torch.device("cuda:0")
     torch.manual_seed(3)
     model = pvlt.pvlt_tiny(pretrained=False, token_hidden_size=768, num_text_tokens=16, loss_type=dict(mlm=1, itm=1, t2i=1, cls=1),
@@ -416,16 +417,13 @@ def test_weight_prep_copies_equal_their_definitions_on_both_lookup_paths():
             got = S.extra[k]
             if suffix == "T" and w.dim() == 2 and name != "t2i_head.score.0.weight":
                 R, Cc = w.shape
-                assert torch.equal(got[:, :R], w.t()) and (got[:, R:] == 0).all(), k
+                assert torch.equal(got[:, :R], t_copy(w)[:, :R]) and (got[:, R:] == 0).all(), k
             elif suffix == "K":
-                out, cin, kh, kw = w.shape
-                assert torch.equal(got, w.permute(0, 2, 3, 1).reshape(out, kh * kw * cin)), k
+                assert torch.equal(got, k_copy(w)), k
             elif suffix == "KT":
-                out, cin, kh, kw = w.shape
-                assert torch.equal(got, w.permute(2, 3, 1, 0).reshape(kh * kw * cin, out)), k
+                assert torch.equal(got, kt_copy(w)), k
             elif suffix == "F":
-                out, cin, kh, kw = w.shape
-                assert torch.equal(got, w.flip(2, 3).permute(1, 2, 3, 0).reshape(cin, kh * kw * out)), k
+                assert torch.equal(got, f_copy(w)), k
 
     check()
     for k in names:
