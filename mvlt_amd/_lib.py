@@ -1,4 +1,4 @@
-"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h, include/mvlt_hip_ema.h, include/mvlt_hip_plan.h, include/mvlt_hip_opt.h, include/mvlt_hip_lamb.h and include/mvlt_hip_loss.h).
+"""ctypes binding of libmvlt_hip.so (the C ABI declared in include/mvlt_hip.h, and the additions of include/mvlt_hip_ext.h, include/mvlt_hip_ema.h, include/mvlt_hip_plan.h, include/mvlt_hip_opt.h, include/mvlt_hip_lamb.h, include/mvlt_hip_loss.h and include/mvlt_hip_ingest.h).
 
 The product path has NO fallback: importing this module without the built library, or calling an op without a
 GPU, raises.  torch is used only for device memory and streams.
@@ -324,6 +324,24 @@ for _name, (_res, _args) in LOSS_PROTOTYPES.items():
 LOSS_VERSION = 1         # include/mvlt_hip_loss.h MVLT_LOSS_VERSION this binding was written against
 if lib.mvlt_loss_version() != LOSS_VERSION:
     raise ImportError(f"loss entry points mismatch: {LIB_PATH} is version {lib.mvlt_loss_version()}, the binding is version {LOSS_VERSION} (stale build? run python -m mvlt_amd.build)")
+
+# The entry points of include/mvlt_hip_ingest.h (uint8 pixels in, resized / flipped / grid-masked fp32 out, docs/ingest.md): a table of their own, bound and
+# version-checked like the one above (tests/test_ingest_cases_cpu.py compares it with that header).
+INGEST_PROTOTYPES = {
+    "mvlt_ingest_version": (_i, []),
+    "mvlt_image_ingest": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "mvlt_image_ingest_resize": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),      # rects_host (parameter 4): a HOST array
+    "mvlt_flip_flags": (_i, [_vp, _i, _f, _u64, _u64, _vp]),
+}
+for _name, (_res, _args) in INGEST_PROTOTYPES.items():
+    if not hasattr(lib, _name):
+        raise ImportError(f"{LIB_PATH} does not export {_name} (include/mvlt_hip_ingest.h): stale build? run python -m mvlt_amd.build")
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _res, _args
+
+INGEST_VERSION = 1       # include/mvlt_hip_ingest.h MVLT_INGEST_VERSION this binding was written against
+if lib.mvlt_ingest_version() != INGEST_VERSION:
+    raise ImportError(f"ingest entry points mismatch: {LIB_PATH} is version {lib.mvlt_ingest_version()}, the binding is version {INGEST_VERSION} (stale build? run python -m mvlt_amd.build)")
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 

@@ -24,12 +24,12 @@ def _sources():
 
 
 def source_hash():
-    """sha256 (first 16 hex digits) over the kernel sources and the seven C ABI headers: what a profile was collected FOR.  tools/roofline_traffic.py
+    """sha256 (first 16 hex digits) over the kernel sources and the eight C ABI headers: what a profile was collected FOR.  tools/roofline_traffic.py
     and tools/step_traffic.py stamp it into their outputs; bench.py drops a committed counter figure whose stamp is not the tree's."""
     import hashlib
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc")))
-    files += [os.path.join(HERE, "..", "include", h) for h in ("mvlt_hip.h", "mvlt_hip_ext.h", "mvlt_hip_ema.h", "mvlt_hip_plan.h", "mvlt_hip_opt.h", "mvlt_hip_lamb.h", "mvlt_hip_loss.h")]
+    files += [os.path.join(HERE, "..", "include", h) for h in ("mvlt_hip.h", "mvlt_hip_ext.h", "mvlt_hip_ema.h", "mvlt_hip_plan.h", "mvlt_hip_opt.h", "mvlt_hip_lamb.h", "mvlt_hip_loss.h", "mvlt_hip_ingest.h")]
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -38,7 +38,7 @@ def source_hash():
 
 def _deps_mtime():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    hdrs += [os.path.join(HERE, "..", "include", h) for h in ("mvlt_hip.h", "mvlt_hip_ext.h", "mvlt_hip_ema.h", "mvlt_hip_plan.h", "mvlt_hip_opt.h", "mvlt_hip_lamb.h", "mvlt_hip_loss.h")]
+    hdrs += [os.path.join(HERE, "..", "include", h) for h in ("mvlt_hip.h", "mvlt_hip_ext.h", "mvlt_hip_ema.h", "mvlt_hip_plan.h", "mvlt_hip_opt.h", "mvlt_hip_lamb.h", "mvlt_hip_loss.h", "mvlt_hip_ingest.h")]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

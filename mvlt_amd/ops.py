@@ -699,6 +699,72 @@ def droppath_scales(out, rates, seed, call):
     return out
 
 
+# ------------------------------------------------------------------ image ingest: uint8 pixels -> fp32 image + grid-masked copy (csrc/ingest.hip, include/mvlt_hip_ingest.h)
+def ingest_table(mean=None, std=None):
+    """the fp32 (3, 256) value table of `image_ingest`, on the CPU, computed the way torchvision's ToTensor (`byte.float().div(255)`) and Normalize
+    (`.sub(mean).div(std)` with fp32 mean / std) compute a pixel, so the kernel's output equals that transform bit for bit by construction"""
+    assert (mean is None) == (std is None)
+    t = torch.arange(256).float().div(255).repeat(3, 1)
+    if mean is not None:
+        m, s = torch.as_tensor(mean, dtype=torch.float32).view(3, 1), torch.as_tensor(std, dtype=torch.float32).view(3, 1)
+        assert bool((s != 0).all())
+        t = t.sub(m).div(s)
+    return t.contiguous()
+
+
+def ingest_norm(mean, std):
+    """the fp32 [6] = {mean[3], std[3]} argument of `image_ingest_resize`, on the CPU"""
+    t = torch.cat([torch.as_tensor(mean, dtype=torch.float32).view(3), torch.as_tensor(std, dtype=torch.float32).view(3)])
+    assert bool((t[3:] != 0).all())
+    return t.contiguous()
+
+
+def _ingest_out_ok(image, masked, flags, B, H, W, patch):
+    assert image.dtype == torch.float32 and image.is_contiguous() and tuple(image.shape) == (B, 3, H, W)
+    assert (masked is None) == (flags is None)
+    if masked is not None:
+        assert masked.dtype == torch.float32 and masked.is_contiguous() and masked.shape == image.shape
+        assert flags.dtype == torch.uint8 and flags.is_contiguous() and patch > 0 and flags.numel() == B * (H // patch) * (W // patch)
+
+
+def image_ingest(src, table, image, masked=None, flags=None, layout=0, patch=16, fill=1e-6):
+    """image (B,3,H,W) fp32 <- table[c][src] for uint8 src (B,H,W,3) (layout 0) or (B,3,H,W) (layout 1); table: `ingest_table(...)` on the device.  With masked / flags
+    (uint8, B * H/patch * W/patch) the same pass writes masked = flags ? fill : image -- `grid_mask_apply`'s result without its launch."""
+    assert src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 4 and layout in (0, 1)
+    B, H, W = (src.shape[0], src.shape[1], src.shape[2]) if layout == 0 else (src.shape[0], src.shape[2], src.shape[3])
+    assert src.shape[3 if layout == 0 else 1] == 3
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.numel() == 768
+    _ingest_out_ok(image, masked, flags, B, H, W, patch)
+    check(L.lib.mvlt_image_ingest(ptr(src), layout, ptr(table), ptr(image), ptr(masked), ptr(flags), B, H, W, patch, fill, stream_ptr()), "mvlt_image_ingest")
+    return image
+
+
+def image_ingest_resize(src, rects, rects_host, image, masked=None, flags=None, flip=None, norm=None, patch=16, fill=1e-6):
+    """image (B,3,H,W) fp32 <- each sample's rectangle rects[b] = (y0, x0, h, w) of the uint8 slab src (B,Hmax,Wmax,3), resampled to (H, W) by the antialiased
+    triangle filter (Pillow's resize(BILINEAR) geometry, fp32 intermediate), mirrored where flip[b] is set, / 255, then (. - mean) / std with norm =
+    `ingest_norm(mean, std)` on the device.  rects: int32 (B,4) on the device; rects_host: the same values in a CPU tensor -- the entry point checks THEM (inside
+    the slab, downscale factor at most 8) before it launches, so no sync is needed.  masked / flags as in `image_ingest`."""
+    assert src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 4 and src.shape[3] == 3
+    B, Hmax, Wmax = src.shape[0], src.shape[1], src.shape[2]
+    assert rects.dtype == torch.int32 and rects.is_contiguous() and tuple(rects.shape) == (B, 4)
+    assert not rects_host.is_cuda and rects_host.dtype == torch.int32 and rects_host.is_contiguous() and tuple(rects_host.shape) == (B, 4)
+    assert image.dim() == 4
+    H, W = image.shape[2], image.shape[3]
+    _ingest_out_ok(image, masked, flags, B, H, W, patch)
+    assert flip is None or (flip.dtype == torch.uint8 and flip.is_contiguous() and flip.numel() == B)
+    assert norm is None or (norm.dtype == torch.float32 and norm.is_contiguous() and norm.numel() == 6)
+    check(L.lib.mvlt_image_ingest_resize(ptr(src), Hmax, Wmax, ptr(rects), rects_host.data_ptr(), ptr(flip), ptr(norm), ptr(image), ptr(masked), ptr(flags),
+                                         B, H, W, patch, fill, stream_ptr()), "mvlt_image_ingest_resize")
+    return image
+
+
+def flip_flags(flip, p, seed, sample0):
+    """flip (uint8 [B]) <- Bernoulli(p) per sample from Philox(seed; sample0 + b, element 0, stream 6): (draw >> 8) < round(p * 2^24)"""
+    assert flip.dtype == torch.uint8 and flip.is_contiguous() and flip.dim() == 1
+    check(L.lib.mvlt_flip_flags(ptr(flip), flip.numel(), p, seed & (2 ** 64 - 1), sample0, stream_ptr()), "mvlt_flip_flags")
+    return flip
+
+
 # ------------------------------------------------------------------ position-embedding resize, GELU backward (csrc/elementwise.hip)
 def loss_compose(losses, weights, out, total):
     """out[0] = total[0] = sum_i weights[i] * losses[i], out[1 + i] = weights[i] * losses[i]; losses: five fp32 device scalars or None"""
