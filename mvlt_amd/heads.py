@@ -4,7 +4,7 @@ import torch
 
 from . import ops
 from ._lib import rowmap
-from .layers import StoreAccess, _empty, linear, linear_bwd
+from .layers import StoreAccess, _empty, linear, linear_bwd, saved
 from .params import pool_zeros
 from .plan import _EVERY, WORD_TABLE, plan_unit
 from .pvlt import EPS_DEFAULT, VOCAB, VOCAB_LD
@@ -76,7 +76,7 @@ class _ClsHeadFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
-        model, name, HW, x4, e, saved, a_map, sink = ctx.pack
+        model, name, HW, x4, e, saved_e, a_map, sink = saved(ctx.pack)
         S, dt, dev, P = model.store, model.compute_dtype, x4.device, StoreAccess(model.store)
         S.queue_finalize()
         u = ctx.unit
@@ -96,7 +96,7 @@ class _ClsHeadFn(torch.autograd.Function):
         de = _empty((B, model.hidden), dt, dev)
         linear_bwd(u.launches["linear"], dl, e, P.g(name + "_head.linear.weight"), None, P.wT(name + "_head.linear.weight"), de)       # (W^T: [768, n_pad])
         dx4, ret = (sink or _GradSink(S)).take(x4.shape, dt, dev) if u.dgrad else (None, None)
-        _embed_ln_bwd(model, name + "_head_embed", de, saved, x4, a_map, B, dx4, a_map, True, u)
+        _embed_ln_bwd(model, name + "_head_embed", de, saved_e, x4, a_map, B, dx4, a_map, True, u)
         ctx.pack = ctx.unit = None
         S.announce_prefix(name + "_head_embed.", name + "_head.")
         return ret, None, None, None, None
@@ -149,7 +149,7 @@ class _MLMFullFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
-        model, HW, x4, e, sv_e, t, sv_t, a_map, sink = ctx.pack
+        model, HW, x4, e, sv_e, t, sv_t, a_map, sink = saved(ctx.pack)
         S, dt, dev = model.store, model.compute_dtype, x4.device
         S.queue_finalize()
         B, N, C = x4.shape
@@ -231,7 +231,7 @@ class _MLMFusedFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gloss):
-        model, HW, xshape, rows, e, sv_e, t, sv_t, logits, lse, acc, positions, labels_sel, tmap, sink = ctx.pack
+        model, HW, xshape, rows, e, sv_e, t, sv_t, logits, lse, acc, positions, labels_sel, tmap, sink = saved(ctx.pack)
         S, dt, dev = model.store, model.compute_dtype, rows.device
         S.queue_finalize()
         B, N, C = xshape

@@ -42,6 +42,15 @@ class StoreAccess:
         return self.S.ln_kwargs()
 
 
+def saved(v):
+    """what a node's forward kept for its backward, or a loud refusal: the node gives it up when its backward has run (ctx.pack / ctx.step = None), so a second
+    backward() over a retained graph has nothing to compute from -- and must not leave the partial sums of the nodes that still could"""
+    if v is None:
+        raise RuntimeError("mvlt_amd: second backward over a retained graph is not supported: this node released what its forward saved when its first "
+                           "backward ran (run the forward again; gradients accumulate over separate forward / backward pairs)")
+    return v
+
+
 def _rows(t):
     return t.numel() // t.shape[-1]
 

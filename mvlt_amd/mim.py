@@ -10,7 +10,7 @@ concatenated buffers.  MFMA operands are the only tensors in the compute dtype.
 import torch
 
 from . import layers, ops
-from .layers import StoreAccess, _empty, linear, linear_bwd
+from .layers import StoreAccess, _empty, linear, linear_bwd, saved
 from .params import pool_zeros
 from .plan import plan_unit
 from ._lib import conv3map, rowmap
@@ -269,7 +269,7 @@ class _MimFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        step = ctx.step
+        step = saved(ctx.step)
         step.S.queue_finalize()
         g2, g3, g4 = step.backward(dout, ctx.sink, ctx.dgrad)
         ctx.step = ctx.sink = None

@@ -411,8 +411,16 @@ class FlatStore:
             from . import ops
             if getattr(self, "_tn_partials", None) is not None:
                 ops.tn_fold_discard(self._tn_partials)         # THIS store's folds (the table is kept per scratch) a pass that raised left pending (nothing, normally): dropped, never run -- their gradients are void, their buffers may be gone
+        # a parameter frozen AFTER a pass gave it a gradient still holds that `.grad`, a view of G -- and kernels of this pass may write its slice all the same
+        # (LayerNorm gradients ride in launches that run for dx, a frozen weight shares a launch with a trainable bias: docs/freeze.md).  torch leaves such a
+        # `.grad` alone, so it is taken out of G here (sync_grads copies it back for a reader of the flat buffer); nothing to do in a pass without one
+        kept = [q for n, q in self.fn_params if not q.requires_grad and q.grad is not None and q.grad.data_ptr() == self.grad(n).data_ptr()]
+        if kept:
+            self.apply_pending_scale()         # (factors still owed to G are owed to these gradients too)
+            for q in kept:
+                q.grad = q.grad.clone()
         live = [(n, q) for n, q in self.fn_params if q.requires_grad]
-        alias = [q.grad is not None and q.grad.data_ptr() == self.grad(n).data_ptr() for n, q in live]
+        alias =[q.grad is not None and q.grad.data_ptr() == self.grad(n).data_ptr() for n, q in live]
         self.all_zeroed_this_pass = not any(alias)     # G is all zeros now: a pass's FIRST writer of a slice may store instead of add (heads._mlm_decoder_bwd)
         self.touched_this_pass = set()
         if not any(alias):

@@ -12,7 +12,7 @@ import torch
 
 from . import layers, ops
 from ._lib import patchmap, rowmap
-from .layers import StoreAccess, _empty, linear, linear_bwd
+from .layers import StoreAccess, _empty, linear, linear_bwd, saved
 from .params import pool_zeros
 from .plan import check_input_size, plan_unit, stage_grids
 from .pvlt import BERT_DROP, EPS_BERT, EPS_BLOCK, EPS_DEFAULT
@@ -551,7 +551,10 @@ class _TrunkFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, images, ids, need_grad, *params):
         step = TrunkStep(model, images, ids, need_grad, getattr(model, "_plan", None))
-        outs = step.forward()
+        # the node's outputs are tensor objects of their own (same storage): the step keeps the stage buffers it wrote, and an output that the node's own context
+        # holds closes a reference cycle through its grad_fn -- a forward whose graph is dropped without a backward (or whose backward raised) then keeps its
+        # activations and its ZeroPool token alive, and every later step finds a forward "pending" (docs/accumulation.md)
+        outs = [o.detach() for o in step.forward()]
         ctx.step = step
         ctx.pool_token, model._pool_token = model._pool_token, None      # this node's life = the time the step's pooled scratch is owned
         ctx.set_materialize_grads(False)          # unused stage outputs send None, not a zero tensor of their size (138 MB at stage 1)
@@ -560,7 +563,7 @@ class _TrunkFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d1, d2, d3, d4):
-        step = ctx.step
+        step = saved(ctx.step)
         S = step.S
         S.queue_finalize()
         step.backward([None, d2, d3, d4])
